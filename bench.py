@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — VisionX-SLAM hot path on MI355X: ms/frame of ORB extract + match + local BA.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`); --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+Everything else the benchmark measures — the per-stage profiling and roofline passes, the
+single-frame latency, the plan-build and drop-in LocalBA::Optimize timings and the CPU baselines —
+runs only with --full; a plain run leaves those fields of the line null.
 
 One step = eight rounds of the pipeline: F frames (F = 8 x the extraction contexts, 24 by default;
 --frames-per-step), each through the hot path, everything resident in HBM before timing starts:
@@ -55,6 +61,35 @@ C5_CAMERAS = 8
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_CAP_BYTES = 60 * 10 ** 6  # all files of one dump together (under 64 MB with their headers)
+
+
+def as_float(a):
+    """A fetched array as float32 / float64: a record array (keypoints, matches) becomes one float64
+    column per field, bytes and integers become float32 / float64 (every value exactly)."""
+    a = np.asarray(a)
+    if a.dtype.names:
+        return np.stack([a[n].astype(np.float64) for n in a.dtype.names], axis=1) if len(a) else \
+            np.zeros((0, len(a.dtype.names)), np.float64)
+    if a.dtype in (np.float32, np.float64):
+        return a
+    return a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+
+
+def dump_outputs(path, arrays):
+    """arrays (name -> array) as path/<name>.npy; over the size cap every array keeps the same
+    fixed, seeded share of its rows (in order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: as_float(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_CAP_BYTES and len(a) > 1:
+            keep = max(1, int(len(a) * DUMP_CAP_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0xD0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 # LocalBA::Options as the reference runner names them (apps/main.cpp:42-47 -> tracking options)
@@ -709,7 +744,7 @@ def bench_c5(args):
         step(t)
     sync()
     stages = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         for c in (front, back):
             c.prof_enable(True)
         nw = max(args.warmup, 3)
@@ -725,9 +760,21 @@ def bench_c5(args):
             c.prof_enable(False)
         stages = {k: (v[0] / max(v[1], 1), v[1] / nw) for k, v in prof.items() if v[1]}
     elapsed = timed_loop(step, args.steps, args.warmup, sync, dist)
+    if args.dump_outputs:
+        # the last rig step's results: every camera of this rank (keypoints, descriptors, matches
+        # against its previous frame) and the window the Schur BA left
+        bank, outs = (args.warmup + args.steps - 1) % 2, {}
+        pre = f"rank{rank}_" if N > 1 else ""
+        for c in range(cams):
+            outs[f"{pre}cam{c}_keypoints"], outs[f"{pre}cam{c}_descriptors"] = front.orb_batch_fetch(bank, c)
+            outs[f"{pre}cam{c}_matches"] = front.match_batch_fetch(c)
+        m_out = m.copy()
+        plan.fetch(m_out)
+        outs[f"{pre}ba_kf_pose"], outs[f"{pre}ba_lm_pos"] = m_out["kf_pose"], m_out["lm_pos"]
+        dump_outputs(args.dump_outputs, outs)
     st = plan.fetch(None)
     lat = []
-    for t in range(5):
+    for t in range(5 if args.full else 0):
         sync()
         t0 = time.perf_counter()
         step(args.steps + args.warmup + t)
@@ -761,7 +808,7 @@ def bench_c5(args):
     cpu = None
     if full_affinity:
         os.sched_setaffinity(0, full_affinity)
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if rank == 0 and N == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as O
 
@@ -774,6 +821,7 @@ def bench_c5(args):
             "metric": "ms/frame (feature-extract+match + BA solve), C5 rig: 8 x 640×480 cameras, 200 KF / 100k pts, "
                       "Schur + MFMA dense pose solve",
             "value": round(value, 4), "unit": "ms/frame", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": False, "scaling": "strong",
             "vs_baseline": None, "dtype": "u8/i32 (FAST, pyramid, BRIEF), f32 (Harris, blur, angle), f64 (BA)",
             "data": "synthetic",
@@ -789,7 +837,7 @@ def bench_c5(args):
                        "ba_window_kf": nk, "ba_landmarks": nl, "orb_features": nf, "plan": info,
                        "scaling": "strong"},
             "ms_per_rig_step": round(1e3 * elapsed / args.steps, 4),
-            "latency_ms_per_rig_step": round(1e3 * float(np.median(lat)), 4),
+            "latency_ms_per_rig_step": round(1e3 * float(np.median(lat)), 4) if lat else None,
             "host_cpus": host_cpus, "parity_vs_unsharded": parity, "rccl": rccl,
             "work_per_step": {"sba_iterations": int(st.iterations), "sba_accepted": int(st.accepted),
                               "sba_initial_cost": float(st.initial_cost), "sba_final_cost": float(st.final_cost)},
@@ -810,6 +858,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the per-stage profiling and roofline passes, the single-frame "
+                         "latency, the plan-build and drop-in LocalBA::Optimize timings and the CPU baselines "
+                         "(a plain run leaves their fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the frames' keypoints, "
+                         "descriptors and matches still resident, the LocalBA window's poses and landmarks) as "
+                         "DIR/<name>.npy, float32 / float64")
     ap.add_argument("--config", default="C3",
                     help="workload C2 / C3 / C4 / C5, or a key=value file with the reference's flag names "
                          "(apps/main.cpp --config; its ba_* keys set the LocalBA options below)")
@@ -829,10 +885,11 @@ def main():
         ap.add_argument(f"--{k}", type=typ, default=None)
     ap.add_argument("--frames", type=int, default=8, help="distinct frames cycled through")
     ap.add_argument("--cpu-sample", type=int, default=30, help="frames timed for the CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
     ap.add_argument("--no-drop-in", action="store_true",
-                    help="skip the per-keyframe drop-in timings (PMC tool runs: the C++ adapter subprocess)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event roofline pass")
+                    help="with --full: skip the per-keyframe drop-in timings (PMC tool runs: the C++ adapter "
+                         "subprocess)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the HIP-event roofline pass")
     ap.add_argument("--ba-cus", type=float, default=0.0,
                     help="fraction of the CUs reserved for the LocalBA context (disjoint CU masks; 0: shared)")
     ap.add_argument("--diag-skip", default="", choices=("", "ba", "match", "extract"),
@@ -983,13 +1040,13 @@ def main():
     # what a drop-in LocalBA::Optimize() adds per call on top of the solve: the window / CSR
     # build from the map snapshot (device build), reported beside `value`
     plan_ms = []
-    for _ in range(5):
+    for _ in range(5 if args.full else 0):
         t0 = time.perf_counter()
         bctx.ba_plan(ba_map, opts, shard_rank=dist.rank, shard_count=N).close()
         plan_ms.append(1e3 * (time.perf_counter() - t0))
-    plan_build_ms = float(np.median(plan_ms))
+    plan_build_ms = float(np.median(plan_ms)) if plan_ms else None
     per_kf = None
-    if N == 1 and not args.no_drop_in:
+    if N == 1 and args.full and not args.no_drop_in:
         # (the C++ drop-in's subprocess inherits this process's CPUs: the whole affinity set, not the 8
         # idlest CPUs the pipeline runs on — its host pool binds itself to one L3 slice of those)
         pinned = os.sched_getaffinity(0)
@@ -1172,7 +1229,7 @@ def main():
     # extraction kernels held the CUs they wait for once doubled the average, r06final2)
     n_chunk = max(4, (args.warmup + 4) // 5)
     n_prof = 5 * n_chunk
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         for c in ctxs:
             c.prof_enable(True)
         chunks = []
@@ -1197,6 +1254,23 @@ def main():
     elapsed = timed_loop(fstep, args.steps, args.warmup, sync, dist)
     enqueue_ms = 1e3 * timed_loop.enqueue_s / args.steps
 
+    if args.dump_outputs:
+        # what the last timed step left for its caller: keypoints and descriptors of its frames still
+        # resident (a context keeps its last three), the matches each matching context fetched last,
+        # and the window LocalBA's last run wrote (every run replays the same resident plan)
+        end, outs = (args.warmup + args.steps) * F, {}
+        pre = f"rank{dist.rank}_" if N > 1 else ""
+        for i in range(end - min(F, 3 * E), end):
+            ci, si = loc(i)
+            name = f"{pre}frame{i - (end - F):02d}"
+            outs[name + "_keypoints"], outs[name + "_descriptors"] = ectxs[ci].orb_fetch(si)
+            if i >= end - (min(F, E) if mon else 1):
+                outs[name + "_matches"] = (ectxs[ci] if mon else mctx).match_fetch()
+        m_out = ba_map.copy()
+        plan.fetch(m_out)
+        outs[pre + "ba_kf_pose"], outs[pre + "ba_lm_pos"] = m_out["kf_pose"], m_out["lm_pos"]
+        dump_outputs(args.dump_outputs, outs)
+
     # ---- roofline pass: the same K steps again, HIP events around every launch of the dominant
     # kernel on the stream it runs on (each bracket also spans that launch's dispatch boundary)
     dominant = max(stages, key=lambda k: stages[k][0] * stages[k][1]) if stages else None
@@ -1210,27 +1284,30 @@ def main():
 
     # single-frame latency: one step alone through the same dependency chain, host enqueue to done
     lat = []
-    for i in range(20):
+    for i in range(20 if args.full else 0):
         sync()
         t0 = time.perf_counter()
         step((args.warmup + args.steps) * F + i)
         sync()
         lat.append(time.perf_counter() - t0)
-    latency_ms = 1e3 * float(np.median(lat))
+    latency_ms = 1e3 * float(np.median(lat)) if lat else None
 
-    # counts for the byte formulas
-    last = (args.warmup + args.steps) * F + 19
+    # the last frame run (the last timed one, or the last of the latency pass): work_per_step, and
+    # the counts for the byte formulas
+    last = (args.warmup + args.steps) * F + len(lat) - 1
     kps, _ = ectxs[loc(last)[0]].orb_fetch(loc(last)[1])
     matches = (ectxs[loc(last)[0]] if mon else mctx).match_fetch()
     st = plan.fetch(None)
     lw = [int(round(w / 1.2 ** l)) for l in range(8)]
     lh = [int(round(h / 1.2 ** l)) for l in range(8)]
     geo = {"W": w, "H": h, "level_px": [a * b for a, b in zip(lw, lh)]}
-    counts = {"n_kp": len(kps), "n_cand": measured_candidates(vxslam, frames_host[last % args.frames], params),
-              "n_q": len(kps), "n_t": len(kps),
-              "n_match": len(matches), "n_pose_obs": info["n_pose_obs"], "n_lm_obs": info["n_lm_obs"],
-              "n_split": info["n_split"], "n_opt": info["n_opt"], "n_kf": info["n_kf"],
-              "ba_iters": int(st.iterations)}
+    counts = None
+    if dominant:
+        counts = {"n_kp": len(kps), "n_cand": measured_candidates(vxslam, frames_host[last % args.frames], params),
+                  "n_q": len(kps), "n_t": len(kps),
+                  "n_match": len(matches), "n_pose_obs": info["n_pose_obs"], "n_lm_obs": info["n_lm_obs"],
+                  "n_split": info["n_split"], "n_opt": info["n_opt"], "n_kf": info["n_kf"],
+                  "ba_iters": int(st.iterations)}
 
     frames_total = args.steps * F * N
     ms_per_step = 1e3 * elapsed / args.steps
@@ -1277,7 +1354,7 @@ def main():
     cpu = None
     if full_affinity:  # (the CPU legs: every core this process may use, as before)
         os.sched_setaffinity(0, full_affinity)
-    if dist.rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if dist.rank == 0 and N == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, frames_host, ba_map, args.cpu_sample)
         cpu["multi_thread"] = cpu_baseline_mt(cfg, frames_host, ba_map, args.cpu_sample)
 
@@ -1296,6 +1373,7 @@ def main():
             "n_gpus": N,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),  # False: a plain run, the fields of the other passes are null
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": False,
             "scaling": args.scaling,
@@ -1329,7 +1407,7 @@ def main():
             },
             # one frame alone through the same dependency chain (host enqueue to completion, median
             # of 20): the per-frame latency; `value` is the pipelined throughput
-            "latency_ms_per_frame": round(latency_ms, 4),
+            "latency_ms_per_frame": round(latency_ms, 4) if lat else None,
             # host time to enqueue one step (Python + C-ABI calls, graph launches), diagnostic: the
             # GPU pipeline cannot run faster than this
             "host_enqueue_ms_per_step": round(enqueue_ms, 4),
@@ -1341,7 +1419,7 @@ def main():
             # the LocalBA plan (SelectKeyFrames + landmark set + CSRs) built on the device from the
             # map snapshot, incl. upload: paid once per LocalBA::Optimize() call of a drop-in
             # (a new keyframe, tracking.cpp:76-84); the timed steps replay a resident plan
-            "ba_plan_build_ms": round(plan_build_ms, 3),
+            "ba_plan_build_ms": round(plan_build_ms, 3) if plan_ms else None,
             # one whole drop-in LocalBA::Optimize() (plan build + solve + results back into the
             # map), median of 7, from the host snapshot and from the device-resident map (N = 1)
             "per_keyframe_ms": per_kf,

@@ -9,7 +9,7 @@ print(d["value"], d["latency_ms_per_frame"], {k: s[k] for k in s if k.startswith
 for r in $(seq $reps); do
   for val in "$@"; do
     export $var=$val
-    v=$(timeout -k 10 300 python bench.py --no-cpu-baseline 2>/dev/null | python -c "$summ") || exit 1
+    v=$(timeout -k 10 300 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "$summ") || exit 1
     echo "$var=$val $v"
   done
 done

@@ -4,7 +4,7 @@ set -o pipefail
 reps=$1; A=$2; B=$3
 for r in $(seq $reps); do
   for o in "$A" "$B"; do
-    v=$(timeout -k 10 300 python bench.py --no-cpu-baseline --no-profile $o 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print(d['value'], d['latency_ms_per_frame'])") || exit 1
+    v=$(timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-profile $o 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read());print(d['value'], d['latency_ms_per_frame'])") || exit 1
     echo "[$o] $v"
   done
 done

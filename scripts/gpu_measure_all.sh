@@ -24,7 +24,7 @@ timeout -k 10 300 python -u scripts/ba_window_sweep.py > $O/ba_window_sweep.txt 
 timeout -k 10 300 python -u scripts/extract_throughput.py > $O/extract_throughput_c3.txt 2>&1 || exit 1
 timeout -k 10 300 python -u scripts/extract_throughput.py C4 > $O/extract_throughput_c4.txt 2>&1 || exit 1
 for c in C2 C4; do
-  timeout -k 10 300 python bench.py --config $c --cpu-sample 10 > $O/bench_${c}.json 2> $O/bench_${c}.err || exit 1
+  timeout -k 10 300 python bench.py --full --config $c --cpu-sample 10 > $O/bench_${c}.json 2> $O/bench_${c}.err || exit 1
 done
 timeout -k 10 300 python -u scripts/sba_bench.py > $O/sba_bench.json 2>&1 || exit 1
 echo "all measurements done"

@@ -1,4 +1,4 @@
-"""Splits a rocprofv3 kernel trace of `python bench.py` into the bench's passes and prints one
+"""Splits a rocprofv3 kernel trace of `python bench.py --full` into the bench's passes and prints one
 kernel's per-dispatch duration per pass, so the HIP-event number bench.py reports
 (roofline.avg_launch_us, measured in the roofline pass) can be compared with rocprof's view of
 the same dispatches.  Passes, in dispatch order of the kernel (launches per step L):

@@ -49,9 +49,10 @@ def test_bench_help_runs_without_gpu():
 
 @pytest.mark.gpu
 def test_bench_json_line():
-    """A short bench run prints exactly one JSON line with the fields the driver reads."""
+    """A short bench run prints exactly one JSON line with the fields the driver reads (--full: the
+    roofline comes from the profiling passes)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -152,7 +153,7 @@ def test_bench_c4_strong_scaling_line():
 def test_bench_c5_line():
     """--config C5: 8 cameras + the Schur BA of the 200 KF / 100k window; the MFMA roofline of the dense
     pose solve (FP64 flops of the symbolic tile factorisation) when it dominates."""
-    d = _json_line(["--config", "C5", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = _json_line(["--config", "C5", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert d["config"]["workload"].startswith("C5") and d["config"]["frames_per_step"] == 8
     assert d["config"]["ba_window_kf"] == 200 and d["config"]["ba_landmarks"] == 100000
     assert d["unit"] == "ms/frame" and d["value"] > 0 and d["work_per_step"]["sba_iterations"] >= 2
@@ -160,6 +161,60 @@ def test_bench_c5_line():
     assert rf is not None
     if rf["bound"] == "mfma":
         assert rf["unit"] == "TFLOP/s" and 0 < rf["frac"] < 1 and rf["flops_per_factorisation"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the steps only: the line keeps its headline fields, the other
+    passes' fields are null; --dump-outputs writes the last step's arrays as float .npy files."""
+    import numpy as np
+
+    d = _json_line(["--config", "C2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert d["full"] is False and d["steps"] == 3 and d["value"] > 0 and d["unit"] == "ms/frame"
+    F = d["config"]["frames_per_step"]
+    # one step is F frames; both figures are rounded to 4 decimals
+    assert abs(d["ms_per_step"] - d["value"] * F) <= (F + 1) * 5e-5 + 1e-9
+    for key in ("roofline", "cpu_baseline", "per_keyframe_ms", "latency_ms_per_frame", "ba_plan_build_ms"):
+        assert d[key] is None, key
+    assert d["stages_us"] == {}
+    files = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 10 ** 6
+    kp, desc, ma = (files[f"frame{F - 1:02d}_{x}.npy"] for x in ("keypoints", "descriptors", "matches"))
+    assert kp.shape == (d["work_per_step"]["keypoints"], 5) and desc.shape == (len(kp), 32)
+    assert ma.shape == (d["work_per_step"]["matches"], 3)
+    from vxslam import synth
+
+    m = synth.make_ba_map(0x5EED0003, 10, 2000, n_streams=1, n_old_kf=2)  # C2's window before LocalBA ran
+    for key in ("kf_pose", "lm_pos"):
+        after = files[f"ba_{key}.npy"]
+        assert after.shape == m[key].shape and np.isfinite(after).all() and not np.array_equal(after, m[key])
+
+
+def test_dump_outputs_floats_and_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs: record arrays become float64 columns, bytes float32; over the cap every
+    array keeps the same seeded rows from run to run."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rec = np.zeros(4, [("a", "<i4"), ("b", "<f4")])
+    rec["a"], rec["b"] = [3, 1, 2, 7], [0.5, 1.5, 2.5, 3.5]
+    arrays = {"rec": rec, "u8": np.arange(64, dtype=np.uint8).reshape(2, 32), "f64": np.arange(3000.0).reshape(-1, 3)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert got["rec"].dtype == np.float64 and got["rec"].tolist() == [[3, 0.5], [1, 1.5], [2, 2.5], [7, 3.5]]
+    assert got["u8"].dtype == np.float32 and np.array_equal(got["u8"], arrays["u8"])
+    assert got["f64"].dtype == np.float64 and np.array_equal(got["f64"], arrays["f64"])
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 6000)
+    arrays = {"u8": np.zeros((40, 32), np.uint8), "f64": arrays["f64"]}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    b, c = (np.load(tmp_path / d / "f64.npy") for d in ("b", "c"))
+    total = sum(np.load(p).nbytes for p in (tmp_path / "b").iterdir())
+    assert total <= 6000 and 0 < len(b) < 1000 and np.array_equal(b, c)
+    assert np.all(np.diff(b[:, 0]) > 0) and np.all(b[:, 1] == b[:, 0] + 1)  # whole rows, in order
 
 
 def test_sba_parity_field_logic():

@@ -139,6 +139,9 @@ private:
         unsigned long long seen = 0;
         {
             std::lock_guard<std::mutex> lk(m_);
+            // (a worker that first runs after ~Pool set stop_ — a process that exits right after
+            // its only job — would otherwise take the final generation as seen and wait for ever)
+            if (stop_) return;
             seen = gen_.load(std::memory_order_relaxed);
         }
         for (;;) {
