@@ -1199,94 +1199,103 @@ __global__ __launch_bounds__(kFT) void k_ba_iter(BAArgs a, FusedArgs f, int it) 
 // ------------------------------------------------------------------ persistent window (k_ba_win)
 // The prologue and every iteration of one LocalBA window in ONE launch (round 6, VERDICT r5 #2a).
 // k_ba_iter's workgroups already exchange nothing but the keyframe rows: a workgroup solves the poses
-// of its own <= kFK keyframe entries from their rows, updates its own landmarks and adds the next
-// iteration's pose-stage terms of its landmarks' observations into those rows.  So the launch
-// boundary between iterations is replaced by point-to-point hand-offs, not a grid barrier:
-//   - iteration i's rows R_i are their own buffer (no reuse inside a run), summed by float atomics
-//     (memory side); after its atomics every wave waits for them (vmcnt(0)), the workgroup meets at a
-//     barrier, and one lane per entry adds 1 to the entry row's arrival counter cnt[i][row], one lane
-//     to done[i] (agent-scope atomics);
-//   - a workgroup solves entry row k of iteration i once cnt[i][k] reaches nprod[k] (the number of
-//     workgroups with an entry on row k, counted at plan build), polled by the entry's own lane with
-//     sc1 loads, and reads the row with sc1 loads (MI355X_MICROARCH.md, hand-off table row 1: atomic
-//     producer, sc1-polled counter, sc1 payload loads; no line of R_i is in any cache before it is
-//     complete: fresh buffers, kernel-start invalidate);
-//   - the stop rule of iteration i - 1 (whether iteration i runs) needs every row of R_(i-1): wave 1
-//     polls done[i - 1] == workgroups (one iteration of slack: almost always already true), sums the
-//     rows' cost / count terms in a fixed order and decides — every workgroup the same, from the
-//     same values; workgroup 0 writes the run's statistics.
+// of its own <= kFK keyframe entries from their rows, updates its own landmarks and produces the next
+// iteration's pose-stage terms of its landmarks' observations for those rows.  So the launch
+// boundary between iterations is replaced by point-to-point hand-offs, not a grid barrier, and the
+// handed-off data is its own flag (cdna_hip_programming.md Guideline 16, form R2):
+//   - a (workgroup, keyframe) entry with observations owns one partial slot of its row per iteration
+//     (the slot k_ba_iter's partial buffer uses: kent's second record, k * maxl + rank).  After the
+//     entry's wave sum the lanes that hold its 29 terms store each double as two 8-byte granules
+//     {32-bit half, 32-bit tag} into part[iteration][slot] (relaxed agent-scope atomic stores: sc1,
+//     write-through; one aligned 8-byte store per granule, so a granule is never torn).  No atomic
+//     add, no drain, no barrier, no counter: a wave's entry is on its way as soon as it is summed;
+//   - every wave of a workgroup sweeps the rows of the entries dealt to it (as in the pose stage):
+//     one lane per term, the two halves of the wave on alternate slots, every slot's granules loaded
+//     (sc1 loads to registers: they bypass this CU's L1) before any tag is checked, then again — only
+//     the granules still missing: re-reading whole rows while the last producers are awaited made
+//     each poll as slow as a full sweep, 0.0503 against 0.0489 ms, r07 — until every tag is the
+//     run's; then the slots are summed in slot order from 0.0 — k_ba_iter's slot combine,
+//     so every run of a plan gives the same bits — and one lane per entry solves the pose;
+//   - the tag is the run's generation + 1 (w.gen, on the device: graph replays see it), never 0.
+//     Granules are per iteration (no reuse inside a run) and runs of one plan are stream-ordered, so
+//     a granule with this run's tag was written in this run for this iteration; whatever an earlier
+//     run (or an iteration an early stop skipped) left carries a smaller tag, the build's memset 0.
+//     Nothing is cleared between runs.  A plan whose generation nears 2^31 runs reports a fault
+//     instead of wrapping: vx_ba_plan_fetch then keeps it on the per-iteration launches;
+//   - ordering: a matching tag arrived in the same 8-byte load as its half, so the value is the
+//     producer's; no other byte is handed over (poses, landmarks and plan tables are the
+//     workgroup's own or written before the launch).  fence(acquire, "wavefront") after a sweep
+//     emits nothing and only keeps the compiler from moving loads above the poll;
+//   - the stop rule of iteration i - 1 (whether iteration i runs) needs the cost / count terms of
+//     every row of iteration i - 1: the row's owner publishes them from its own sum as tagged
+//     granules (stop[i - 1][row]); wave 1 sweeps them one iteration later (almost always already
+//     there), sums them in a fixed order and decides — every workgroup the same, from the same
+//     values; workgroup 0 writes the run's statistics;
+//   - workgroup 0 bumps the generation at its end.  Every workgroup stores the tag into hello[b]
+//     right after reading the generation, and workgroup 0's wave 1 sweeps hello[] in iteration 0
+//     (max_iter >= 1, and a stop is decided in iteration 1 at the earliest): it cannot reach its end
+//     before every workgroup has read the generation, whatever the entries' topology, M = 1 and
+//     early stops included.
 // Everything a workgroup loads that no iteration changes (block / entry records, landmark-stage
 // observations, the landmarks' slots and runs, the first pose-stage round) is loaded once; the
-// entries' poses and the landmark positions stay in registers / LDS.  Buffers by run parity (the
-// run's generation, w.gen): a run zeroes the other parity's rows and counters for the next run (plain
-// stores, written back at the kernel's end).  Every workgroup must be resident at once (nb <= CUs,
-// one 512-thread workgroup per CU); every wait is bounded (kWinSpinTicks): a wait that runs out sets
-// the state's fault flag, every workgroup leaves, and vx_ba_plan_fetch re-runs the window with the
-// per-iteration launches (plan->win_off) — two persistent windows on one device at once could
-// otherwise hold each other's compute units.
+// entries' poses and the landmark positions stay in registers / LDS.  Every workgroup must be
+// resident at once (nb <= CUs, one 512-thread workgroup per CU); every wait is bounded
+// (kWinSpinTicks): a wait that runs out sets the state's fault flag, every workgroup leaves, and
+// vx_ba_plan_fetch re-runs the window with the per-iteration launches (plan->win_off) — two
+// persistent windows on one device at once could otherwise hold each other's compute units.
+typedef unsigned long long wgran;  // {value half (low 32 bits), tag (high 32 bits)}
 struct WinArgs {
-    double* rows;      // [2][max_iter][n_kf][kStride]
-    int* cnt;          // [2][max_iter][n_kf] arrivals per row
-    int* done;         // [2][max_iter][32] workgroups done with iteration i's pose stage (own lines)
-    const int* nprod;  // [n_kf] workgroups with an entry on the row
-    int* gen;          // run generation (parity = gen & 1), bumped by workgroup 0 at the run's end
-    int* fault;        // set when a wait ran out (every workgroup then leaves)
+    wgran* part;         // [max_iter][n_kf * maxl + 1][kStride][2] the rows' partial slots
+    wgran* stop;         // [max_iter][n_kf][4] the owners' cost | count terms of their rows
+    unsigned* hello;     // [workgroups] tag once the workgroup has read the generation
+    int* gen;            // run generation, bumped by workgroup 0 at the run's end
+    int* fault;          // set when a wait ran out (every workgroup then leaves)
+    int bias;            // $VX_BA_WIN_TEST_FAULT: row 0 waits for one more slot, which nobody fills
 };
 constexpr long long kWinSpinTicks = 20'000'000;  // 200 ms of the 100 MHz wall clock
+constexpr int kWinGenMax = 0x7ffffff0;           // (tags stay below 2^31: no wrap-around)
+// slots per lane and sweep pass (two lanes per term: 2 kWinSB slots a pass; C3's rows have ~17).
+// 16 — every row in one pass — measured slower: LocalBA alone 0.0534 against 0.0503 ms, r07
+constexpr int kWinSB = 8;
+constexpr int kWinSStride = kStride + 1;  // staged row sums in LDS (odd: the solving lanes' reads spread)
 // k_ba_win's LDS: k_ba_iter's plus a second set of pose slots
 constexpr size_t win_lds(int ft) {
     return fused_lds(ft) + (size_t)kFK * kLdsStride * sizeof(double) + (size_t)ft * (16 + 16 + 12);
 }
 static_assert(win_lds(kFTSmall) <= 160 * 1024, "k_ba_win LDS exceeds gfx950's 160 KB per workgroup");
+static_assert(kFK * kWinSStride <= 9 * kFTSmall, "k_ba_win stages the row sums in the landmark stage's terms");
 
 __device__ __forceinline__ int ld_sc1(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double ld_sc1(const double* p) {
+__device__ __forceinline__ unsigned ld_sc1(const unsigned* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void add_agent(int* p, int v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ wgran ld_sc1(const wgran* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// lanes with want: spin until *p >= target (each lane its own counter); false when the wait ran out
-// or another workgroup reported a fault
-#ifndef VX_WIN_POLLS
-#define VX_WIN_POLLS 1
-#endif
-__device__ __forceinline__ bool win_wait(const int* p, int target, bool want, int* fault) {
-    const long long t0 = wall_clock64();
-    bool ok = true;
-    __builtin_amdgcn_s_setprio(0);  // (a polling wave leaves the SIMD to co-resident waves)
-    // VX_WIN_POLLS polls in flight: each pass issues the next poll before it checks the oldest (the
-    // loads are independent sc1 loads; the compiler waits for the oldest only).  Two or three in
-    // flight measured no faster than one (LocalBA alone 0.0508-0.0518 ms with three against
-    // 0.0498-0.0509 with one, r06s2 poll A/B): one stays the default
-    // (every lane loads — lanes without a wait read the fault word — so no exec-masked branch makes
-    // the compiler drain every load at its join)
-    const int* const pp = want ? p : fault;
-    int q[VX_WIN_POLLS];
-#pragma unroll
-    for (int i = 0; i + 1 < VX_WIN_POLLS; ++i) q[i] = ld_sc1(pp);
-    for (int k = 0;; ++k) {
-        q[VX_WIN_POLLS - 1] = ld_sc1(pp);
-        const bool pend = want && ok && q[0] < target;
-#pragma unroll
-        for (int i = 0; i + 1 < VX_WIN_POLLS; ++i) q[i] = q[i + 1];
-        if (!__any(pend)) break;
-        if ((k & 15) == 15) {
-            if (ld_sc1(fault) || wall_clock64() - t0 > kWinSpinTicks) {
-                if (pend) ok = false;
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);  // (longer naps between polls measured the same: r06g)
+// one double as its two tagged granules (each an aligned 8-byte sc1 store)
+__device__ __forceinline__ void st_gran2(wgran* g, double v, unsigned tag) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v), t = (unsigned long long)tag << 32;
+    __hip_atomic_store(g, t | (u & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(g + 1, t | (u >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double gran2_value(wgran lo, wgran hi) {
+    return __longlong_as_double((long long)((lo & 0xffffffffull) | (hi << 32)));
+}
+// a sweep that found a tag missing: naps, and every 16th pass checks the fault word and the clock.
+// Wave-uniform; true when the wait ran out or another workgroup reported a fault (the fault word is
+// then set)
+__device__ __forceinline__ bool win_spin_fail(int& k, long long t0, int* fault) {
+    if ((++k & 15) == 0 && (ld_sc1(fault) || wall_clock64() - t0 > kWinSpinTicks)) {
+        if ((threadIdx.x & 63) == 0) __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return true;
     }
-    __builtin_amdgcn_s_setprio(3);
-    return __all(ok);
+    __builtin_amdgcn_s_sleep(1);  // (longer naps between polls measured the same: r06g)
+    return false;
 }
 
-// (232 VGPRs, two waves per SIMD.  Sized for three — 168 VGPRs, so that a third wave of the other
-// streams' kernels fits beside it — it spills outside the observation rounds: LocalBA alone 0.067
-// against 0.054 ms, the C3 pipeline 0.074 against 0.063 ms/frame, r06i)
+// (239 VGPRs, no scratch, two waves per SIMD.  Sized for three — 168 VGPRs, so that a third wave of
+// the other streams' kernels fits beside it — it spills outside the observation rounds: LocalBA
+// alone 0.067 against 0.054 ms, the C3 pipeline 0.074 against 0.063 ms/frame, r06i)
 template <int kFT>
 __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w) {
     constexpr int kFW = kFT / 64;
@@ -1294,6 +1303,7 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     __builtin_amdgcn_s_setprio(3);
     extern __shared__ __attribute__((aligned(16))) double fl[];
     __shared__ int4 s_ke[kFK];
+    __shared__ int s_kd[kFK];  // the entry's partial slot (k * maxl + rank; -1: no observations)
     __shared__ int s_act, s_fault;
     // two pose-slot sets (T 8 | R 9 | C 4 | flags per entry): iteration it solves from set (it - 1) & 1
     // into set it & 1, so a wave still in the previous pose stage (no barrier closes it) reads poses
@@ -1311,18 +1321,25 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     const size_t base = (size_t)b * kFT;
     const int4* KE = f.kent + (size_t)b * kFK * 2;
     const int M = a.max_iter, nk = a.n_kf, nb = (int)gridDim.x;
-    const size_t rows_per = (size_t)M * nk * kStride;
+    const int nslot = nk * f.maxl;  // (slot nslot: the one nobody fills, WinArgs::bias)
     // ---- loads: the run generation, then everything the window keeps (k_ba_iter's prologue loads
     // plus the landmark-stage records its iteration launches load again and again)
-    const int par = w.gen[0] & 1;
-    double* const R = w.rows + (size_t)par * rows_per;
-    int* const cnt = w.cnt + (size_t)par * M * nk;
-    int* const done = w.done + (size_t)par * M * 32;
+    const int gen = w.gen[0];
+    const unsigned tag = (unsigned)gen + 1u;
+    if (gen < 0 || gen >= kWinGenMax) {  // (every workgroup alike: the fetch falls back for good)
+        if (tid == 0) __hip_atomic_store(w.fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    if (tid == 0) __hip_atomic_store(w.hello + b, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int wvu = __builtin_amdgcn_readfirstlane(wv);
     const int4 B = f.blk[(size_t)b * (1 + kFW / 2)];
     const int4 WB = f.blk[(size_t)b * (1 + kFW / 2) + 1 + (wvu >> 1)];
     int4 ke = make_int4(-1, 0, 0, 0);
-    if (tid < kFK) ke = KE[2 * tid];
+    int kd = -1;
+    if (tid < kFK) {
+        ke = KE[2 * tid];
+        kd = KE[2 * tid + 1].x;
+    }
     const int4 orec0 = f.lobs_rec[base + tid];
     const double2 ouv0 = f.lobs_uv[base + tid];
     const int lslot0 = f.lm_slot[base + tid];
@@ -1346,7 +1363,6 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     first_round();
     // the entry's state lives in its LDS slot (T 8 | R 9 | C 4 | flags), not in registers
     double ev[13];
-    int np = 0;
     const int row = ke.x & 0x3fffffff;
     if (tid < kFK && ke.x >= 0) {
 #pragma unroll
@@ -1354,16 +1370,6 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
 #pragma unroll
         for (int j = 0; j < 4; ++j) ev[8 + j] = a.kf_intr[4 * row + j];
         ev[12] = (double)a.kf_flags[row];
-        np = w.nprod[row];
-    }
-    // the next run's buffers (the other parity) zeroed; its rows were last read by the previous run
-    {
-        double* Ro = w.rows + (size_t)(par ^ 1) * rows_per;
-        for (size_t i = (size_t)b * kFT + tid; i < rows_per; i += (size_t)nb * kFT) Ro[i] = 0.0;
-        int* co = w.cnt + (size_t)(par ^ 1) * M * nk;
-        for (int i = b * kFT + tid; i < M * nk; i += nb * kFT) co[i] = 0;
-        int* dn = w.done + (size_t)(par ^ 1) * M * 32;
-        for (int i = b * kFT + tid; i < M * 32; i += nb * kFT) dn[i] = 0;
     }
     if (b == 0 && tid < 16) {  // (the statistics of this run, as stop_rule(0) starts them)
         a.state->cost[tid] = 0.0;
@@ -1379,7 +1385,10 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     s_run[3 * tid] = run0.x;
     s_run[3 * tid + 1] = run0.y;
     s_run[3 * tid + 2] = lslot0;
-    if (tid < kFK) s_ke[tid] = ke;
+    if (tid < kFK) {
+        s_ke[tid] = ke;
+        s_kd[tid] = kd;
+    }
     if (tid == 0) s_fault = 0;
     if (tid < kFK && ke.x >= 0) {  // iteration 0's pose stage reads the initial poses (set 1)
         double Rm[9];
@@ -1397,11 +1406,14 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     __syncthreads();
 
     // ---- pose stage of iteration `itn` from the poses in set (itn - 1) & 1 and the landmarks in lpos,
-    // added into R_itn; then the hand-off (every wave's atomics retired, barrier, one arrival per
-    // entry row).  (The barrier does not protect the pose slots: the next solve writes the other set.)
+    // each entry's terms into its own partial slot of iteration itn as tagged granules: that store is
+    // the hand-off.  No barrier closes the stage: the LDS it reads (s_ke / s_kd: never rewritten; pose
+    // set (itn - 1) & 1: the next solve writes the other set; lpos: next written behind phase A's
+    // barrier) is not written before every wave has passed the next barrier, and what the next
+    // phase A writes (the staged sums in `terms`, s_act) it does not read.
     auto pose_stage = [&](int itn) {
         int r = 0;
-        double* const Rn = R + (size_t)itn * nk * kStride;
+        wgran* const Pn = w.part + (size_t)itn * (nslot + 1) * (2 * kStride);
         const double* const kslot = ks0 + ((itn - 1) & 1) * kFK * kLdsStride;
         for (int j = wv; j < n_ent; j += kFW) {
             const int4 e = s_ke[j];
@@ -1441,25 +1453,51 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
                 pose_obs_accum<true>(a, T, Rr, C, P, uv, v, valid);
             }
             const double tot = wave_sum32(v);
-            if ((lane & 1) == 0 && (lane >> 1) < kNTerms)
-                unsafeAtomicAdd(Rn + (size_t)(e.x & 0x3fffffff) * kStride + (lane >> 1), tot);
+            const int kdj = s_kd[j];
+            if ((lane & 1) == 0 && (lane >> 1) < kNTerms && kdj >= 0)
+                st_gran2(Pn + ((size_t)kdj * kStride + (lane >> 1)) * 2, tot, tag);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (this wave's adds are done at the memory side)
-        // the hand-off after the workgroup's barrier, one lane per entry row (signalling wave by wave,
-        // each wave's entries as soon as its own adds retired, measured 35 % slower: r06e/r06g)
-        __syncthreads();
-        if (tid < kFK && ke.x >= 0) add_agent(cnt + (size_t)itn * nk + row, 1);
-        if (tid == kFK) add_agent(done + (size_t)itn * 32, 1);
     };
-    // ---- stop rule of iteration ip (local_ba.cpp:240-247) from every row of R_ip, by wave 1 of every
-    // workgroup (the same values summed in the same order: the same decision everywhere)
+    // ---- workgroup 0, iteration 0: every workgroup has read the generation (see the header)
+    auto hello_sweep = [&]() -> int {
+        const long long t0 = wall_clock64();
+        for (int spins = 0;;) {
+            bool ok = true;
+            for (int q = lane; q < nb; q += 64) ok &= ld_sc1(w.hello + q) == tag;
+            if (__all(ok)) return 1;
+            if (win_spin_fail(spins, t0, w.fault)) return -1;
+        }
+    };
+    // ---- stop rule of iteration ip (local_ba.cpp:240-247) from the owners' cost / count terms of
+    // every row of iteration ip, by wave 1 of every workgroup (the same values summed in the same
+    // order: the same decision everywhere)
     double last = 1.7976931348623157e308;
-    auto decide = [&](int ip) -> int {
-        if (!win_wait(done + (size_t)ip * 32, nb, lane == 0, w.fault)) return -1;
+    // (d: the first 64 rows' granules, requested by the caller ahead of its own sweep so that their
+    // round trip is not in front of it; they are the first poll)
+    auto decide_issue = [&](int ip, wgran (&d)[4]) {
+        const wgran* const g = w.stop + ((size_t)ip * nk + (lane < nk ? lane : 0)) * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] = ld_sc1(g + i);
+    };
+    auto decide = [&](int ip, const wgran (&d)[4]) -> int {
+        const wgran* const sp = w.stop + (size_t)ip * nk * 4;
+        const long long t0 = wall_clock64();
+        int spins = 0;
         double tot = 0.0, cn = 0.0;
-        for (int q = lane; q < nk; q += 64) {
-            tot += ld_sc1(R + ((size_t)ip * nk + q) * kStride + 27);
-            cn += ld_sc1(R + ((size_t)ip * nk + q) * kStride + 28);
+        for (int q0 = 0; q0 < nk; q0 += 64) {  // (lane-strided, as the sums of complete rows were)
+            const bool live = q0 + lane < nk;
+            const wgran* const g = sp + (size_t)(live ? q0 + lane : 0) * 4;
+            wgran c0 = d[0], c1 = d[1], n0 = d[2], n1 = d[3];
+            for (bool first = q0 == 0;; first = false) {
+                if (!first) c0 = ld_sc1(g), c1 = ld_sc1(g + 1), n0 = ld_sc1(g + 2), n1 = ld_sc1(g + 3);
+                const bool ok = !live || ((unsigned)(c0 >> 32) == tag && (unsigned)(c1 >> 32) == tag &&
+                                          (unsigned)(n0 >> 32) == tag && (unsigned)(n1 >> 32) == tag);
+                if (__all(ok)) break;
+                if (win_spin_fail(spins, t0, w.fault)) return -1;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            tot += live ? gran2_value(c0, c1) : 0.0;
+            cn += live ? gran2_value(n0, n1) : 0.0;
         }
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1) {
@@ -1491,22 +1529,91 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
     for (int it = 0; it < M; ++it) {
         double* const kslot = ks0 + (it & 1) * kFK * kLdsStride;
         const double* const kprev = ks0 + ((it + 1) & 1) * kFK * kLdsStride;
-        // ---- A: wave 0 waits for its entries' rows of R_it, reads and solves them; wave 1 decides
-        // whether iteration it runs (the stop rule of it - 1)
-        if (wv == 0) {
-            const bool want = tid < kFK && ke.x >= 0;
-            const bool ok = win_wait(cnt + (size_t)it * nk + row, np, want, w.fault);
-#ifndef VX_WIN_TRACE_LM
-            if (it < 5) VX_KT(1 + 3 * it);
-#endif
-            if (!ok && lane == 0) s_fault = 1;
-            if (want && ok) {
-                double S[kNTerms];
-                const double* rp = R + ((size_t)it * nk + row) * kStride;
+        // ---- A: every wave sweeps the partial slots of its entries' rows (entries dealt as in the
+        // pose stage), sums them in slot order and solves its entries; wave 1 also decides whether
+        // iteration it runs (the stop rule of it - 1: its granules have had an iteration to arrive
+        // and are requested ahead of the wave's own sweep)
+        wgran dgr[4] = {0, 0, 0, 0};
+        if (wv == 1 && it > 0) decide_issue(it - 1, dgr);
+        {
+            const int h = lane >> 5, t = lane & 31;  // half h of the wave: slots s0 + 2 i + h, term t
+            const wgran* const Pi = w.part + (size_t)it * (nslot + 1) * (2 * kStride);
+            double* const stage = terms;  // [kFK][kWinSStride] (the landmark stage writes terms behind the barrier)
+            const long long t0 = wall_clock64();
+            int spins = 0;
+            bool okw = true;
+            __builtin_amdgcn_s_setprio(0);
+            for (int j = wv; j < n_ent && okw; j += kFW) {
+                const int4 e = s_ke[j];
+                if (e.x < 0) continue;  // a hole in the entry positions
+                const int erow = e.x & 0x3fffffff;
+                const int ns = e.y + (erow == 0 ? w.bias : 0);
+                double acc = 0.0;
+                for (int s0 = 0; s0 < ns && okw; s0 += 2 * kWinSB) {
+                    wgran g0[kWinSB], g1[kWinSB];
+                    // have: bit i = the lane's slot i is in (both tags matched) or is nothing to wait for
+                    unsigned have = 0;
 #pragma unroll
-                for (int t = 0; t < kNTerms; ++t) S[t] = ld_sc1(rp + t);
-                double* sl = kslot + tid * kLdsStride;
-                const double* sp = kprev + tid * kLdsStride;
+                    for (int i = 0; i < kWinSB; ++i) {
+                        g0[i] = g1[i] = 0;
+                        if (!(s0 + 2 * i + h < ns && t < kNTerms)) have |= 1u << i;
+                    }
+                    for (;;) {
+                        // every missing slot's loads go out before any tag is checked; a pass asks
+                        // again only for what the pass before did not find (a matched granule is
+                        // final), so the passes that wait for the last producers are a few loads
+#pragma unroll
+                        for (int i = 0; i < kWinSB; ++i)
+                            if (!((have >> i) & 1)) {
+                                const int q = s0 + 2 * i + h;
+                                const int slot = q < e.y ? erow * f.maxl + q : nslot;
+                                const wgran* g = Pi + ((size_t)slot * kStride + t) * 2;
+                                g0[i] = ld_sc1(g);
+                                g1[i] = ld_sc1(g + 1);
+                            }
+#pragma unroll
+                        for (int i = 0; i < kWinSB; ++i)
+                            if (!((have >> i) & 1) && (unsigned)(g0[i] >> 32) == tag && (unsigned)(g1[i] >> 32) == tag)
+                                have |= 1u << i;
+                        if (__all(have == (1u << kWinSB) - 1)) break;
+                        if (win_spin_fail(spins, t0, w.fault)) {
+                            okw = false;
+                            break;
+                        }
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no load moves above the poll)
+                    // slot order from 0.0, as k_ba_iter's slot combine (+0.0 past the end: exact);
+                    // the sum is lane t's (half 0), which gets the odd slots from lane t + 32
+#pragma unroll
+                    for (int i = 0; i < kWinSB; ++i) {
+                        const bool live = s0 + 2 * i + h < ns && t < kNTerms;
+                        const double v = live ? gran2_value(g0[i], g1[i]) : 0.0;
+                        const double vo = __shfl(v, t + 32, 64);
+                        acc += v;
+                        acc += vo;
+                    }
+                }
+                if (lane < kNTerms) stage[j * kWinSStride + lane] = acc;
+                // the row's owner hands its cost / count terms to the stop rule
+                if (okw && (e.x & (1 << 30)) && (lane == 27 || lane == 28))
+                    st_gran2(w.stop + ((size_t)it * nk + erow) * 4 + (lane - 27) * 2, acc, tag);
+            }
+            __builtin_amdgcn_s_setprio(3);
+#ifndef VX_WIN_TRACE_LM
+            if (wv == 0 && it < 5) VX_KT(1 + 3 * it);
+#endif
+            if (!okw && lane == 0) s_fault = 1;
+            // (the wave's own LDS stores, read back by its own lanes: LDS keeps a wave's order)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int js = wv + kFW * lane;  // lane i solves the wave's i-th entry
+            if (okw && js < n_ent && s_ke[js < kFK ? js : 0].x >= 0) {
+                double S[kNTerms];
+#pragma unroll
+                for (int q = 0; q < kNTerms; ++q) S[q] = stage[js * kWinSStride + q];
+                double* sl = kslot + js * kLdsStride;
+                const double* sp = kprev + js * kLdsStride;
                 double T[8], Rm[9];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) T[j] = sp[j];
@@ -1516,8 +1623,11 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
 #pragma unroll
                 for (int j = 0; j < 9; ++j) sl[8 + j] = Rm[j];
             }
-        } else if (wv == 1) {
-            const int act = it == 0 ? 1 : decide(it - 1);
+        }
+        if (wv == 1) {
+            __builtin_amdgcn_s_setprio(0);  // (a polling wave leaves the SIMD to co-resident waves)
+            const int act = it == 0 ? (b == 0 ? hello_sweep() : 1) : decide(it - 1, dgr);
+            __builtin_amdgcn_s_setprio(3);
             if (lane == 0) {
                 s_act = act > 0;
                 if (act < 0) s_fault = 1;
@@ -1570,24 +1680,15 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
         if (wv == 0 && it < 4) VX_KT(3 + 3 * it);
     }
     // ---- the last iteration's statistics (a stop inside the loop wrote them), then the next run's
-    // parity; workgroup 0 gets here only after every workgroup's first arrival (its waits above), so
-    // every workgroup has read the generation
+    // generation: workgroup 0's wave 1 swept hello[] in iteration 0, so every workgroup has read
+    // this run's (a faulted run keeps its generation: the plan leaves the window for good)
     if (b == 0 && wv == 1 && !s_fault && s_act) {
-        const int r = decide(M - 1);
+        wgran dgr[4];
+        decide_issue(M - 1, dgr);
+        const int r = decide(M - 1, dgr);
         if (r < 0 && lane == 0) s_fault = 1;
     }
-    if (b == 0 && wv == 1 && lane == 0 && !s_fault) w.gen[0] = w.gen[0] + 1;
-}
-
-// plan build: nprod[row] = workgroups with an entry on the row (the arrivals k_ba_win waits for)
-// (bias: $VX_BA_WIN_TEST_FAULT=1 adds one arrival to row 0 that never comes, so the run's waits run
-// out: the test of the fault path, tests/test_gpu_parity.py)
-__global__ void k_win_nprod(const int4* kent, int nb, int* nprod, int bias) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nb * kFK) return;
-    const int x = kent[2 * (size_t)i].x;
-    if (x >= 0) atomicAdd(nprod + (x & 0x3fffffff), 1);
-    if (i == 0) atomicAdd(nprod, bias);
+    if (b == 0 && wv == 1 && lane == 0 && !s_fault) w.gen[0] = gen + 1;
 }
 
 // sharded plans: each keyframe row's partial slots summed in slot order (the slots of a row no group
@@ -1932,18 +2033,16 @@ int fused_finish(vx_ctx* c, vx_ba_plan* p, int nb, int ft, int maxl, size_t n_pp
             at += (bytes + 255) & ~(size_t)255;
             return o;
         };
-        p->win_rows_off = take(2 * M * nk * kStride * sizeof(double));
-        p->win_cnt_off = take(2 * M * nk * sizeof(int));
-        p->win_done_off = take(2 * M * 32 * sizeof(int));
-        p->win_nprod_off = take(nk * sizeof(int));
+        // per iteration every partial slot of every row plus one slot that nobody fills (what
+        // $VX_BA_WIN_TEST_FAULT makes row 0 wait for: the test of the fault path,
+        // tests/test_gpu_parity.py); zeroed once here (tag 0 is no run's), never between runs
+        p->win_part_off = take(M * (nk * (size_t)maxl + 1) * kStride * 2 * sizeof(wgran));
+        p->win_stop_off = take(M * nk * 4 * sizeof(wgran));
+        p->win_hello_off = take((size_t)nb * sizeof(unsigned));
         p->win_gen_off = take(sizeof(int));
+        p->win_bias = getenv("VX_BA_WIN_TEST_FAULT") ? 1 : 0;
         VX_HIP(c, p->f_win.ensure(at));
         VX_HIP(c, hipMemsetAsync(p->f_win.p, 0, at, c->stream));
-        hipLaunchKernelGGL(k_win_nprod, dim3((unsigned)((nb * kFK + 255) / 256)), dim3(256), 0, c->stream,
-                           reinterpret_cast<const int4*>(T + F.kent), nb,
-                           reinterpret_cast<int*>(p->f_win.as<uint8_t>() + p->win_nprod_off),
-                           getenv("VX_BA_WIN_TEST_FAULT") ? 1 : 0);
-        VX_LAUNCH_CHECK(c, "k_win_nprod");
         p->f_persist = true;
     }
     p->f_stop_b = stop_b;
@@ -2594,11 +2693,11 @@ bool peer_requested() {
 WinArgs make_win_args(vx_ba_plan* p) {
     uint8_t* W = p->f_win.as<uint8_t>();
     WinArgs w{};
-    w.rows = reinterpret_cast<double*>(W + p->win_rows_off);
-    w.cnt = reinterpret_cast<int*>(W + p->win_cnt_off);
-    w.done = reinterpret_cast<int*>(W + p->win_done_off);
-    w.nprod = reinterpret_cast<const int*>(W + p->win_nprod_off);
+    w.part = reinterpret_cast<wgran*>(W + p->win_part_off);
+    w.stop = reinterpret_cast<wgran*>(W + p->win_stop_off);
+    w.hello = reinterpret_cast<unsigned*>(W + p->win_hello_off);
     w.gen = reinterpret_cast<int*>(W + p->win_gen_off);
+    w.bias = p->win_bias;
     w.fault = reinterpret_cast<int*>(p->state.as<uint8_t>() + offsetof(BAState, fault));
     return w;
 }

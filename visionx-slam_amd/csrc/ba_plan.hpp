@@ -46,11 +46,13 @@ struct vx_ba_plan {
     vx::DevBuf f_costpart;       // compact {cost, observations} of every partial slot (stop rule)
     vx::DevBuf f_arow;           // $VX_BA_ATOMIC_ROWS: 3 rotating n_kf x 32 per-row sums (float atomics)
     bool f_atomic = false;
-    // persistent window (k_ba_win, one launch per run): rows / arrival counters by run parity,
-    // nprod, the generation word (ba.hip WinArgs); win_off after a run whose wait ran out
+    // persistent window (k_ba_win, one launch per run): the rows' tagged partial slots per
+    // iteration, the owners' stop-rule terms, the workgroups' hello words, the generation word
+    // (ba.hip WinArgs); win_off after a run whose wait ran out
     vx::DevBuf f_win;
     bool f_persist = false, win_off = false;
-    size_t win_rows_off = 0, win_cnt_off = 0, win_done_off = 0, win_nprod_off = 0, win_gen_off = 0;
+    size_t win_part_off = 0, win_stop_off = 0, win_hello_off = 0, win_gen_off = 0;
+    int win_bias = 0;            // $VX_BA_WIN_TEST_FAULT at plan build (WinArgs::bias)
     int f_stop_b = 0;            // workgroup running the stop rule
     vx::PinnedBuf f_stage;                                        // their host staging block
     vx::PinnedBuf fetch_host;  // vx_ba_plan_fetch: the state, both pose parities and the positions, one copy each
