@@ -25,6 +25,9 @@
  *                                                                core/frontend/tracking.cpp:856-945
  *   vx_pnp_ransac         <- cv::solvePnPRansac in Tracking::TrackWithPnP
  *                                                                core/frontend/tracking.cpp:414-423
+ *   vx_track_pnp_*        <- Tracking::TrackWithPnP after Match(): distance filter, 3D-2D pairs over
+ *                            Map::GetLandmark, solvePnPRansac, ComputeParallax
+ *                                                                core/frontend/tracking.cpp:332-455
  *   vx_essential_ransac   <- cv::findEssentialMat + cv::recoverPose in
  *                            Tracking::EstimatePoseByEssential   core/frontend/tracking.cpp:503-547
  *   vx_dmap_*             <- visionx::Map (map.h:13-35) kept resident on the device, updated like
@@ -574,6 +577,78 @@ int vx_pnp_ransac(vx_ctx* ctx, const float* obj_pts, const float* img_pts, int n
 int vx_pnp_ransac_batch(vx_ctx* ctx, int n_problems, const int32_t* offsets, const float* obj_pts,
                         const float* img_pts, const double* intr4, const vx_pnp_options* opt,
                         uint8_t* inlier_mask, vx_pnp_result* out);
+
+/* ---------------------------------------------------------------- TrackWithPnP on the device (track.hip)
+ * <- Tracking::TrackWithPnP after Match(last_keyframe, curr) (tracking.cpp:332-455): the distance
+ *    filter (:342-355), the 3D-2D pair build over Map::GetLandmark (:364-400), solvePnPRansac
+ *    (:414-423) and ComputeParallax (:449, :548-560) as ONE stream-ordered sequence over data that is
+ *    already on the device — the match list, the current frame's keypoints, the resident map — with
+ *    one synchronisation, in the fetch. */
+typedef struct {
+    int32_t min_matches;        /* Tracking::Options::min_matches 50 (tracking.cpp:357) */
+    int32_t min_inliers;        /* Tracking::Options::min_inliers 30 (tracking.cpp:402, :425) */
+    vx_pnp_options pnp;         /* max_iterations < 0: min(100, 2 * n_pairs), computed on the device
+                                   (tracking.cpp:421); reproj 2.0, conf 0.99, 20 LM, seed 0x5EED */
+} vx_track_options;
+
+#define VX_TRACK_OK 0
+#define VX_TRACK_FEW_MATCHES 1   /* filtered matches < min_matches          (tracking.cpp:357) */
+#define VX_TRACK_FEW_PAIRS 2     /* 3D-2D pairs < min_inliers               (tracking.cpp:402) */
+#define VX_TRACK_PNP_FAILED 3    /* !ok || inliers < min_inliers            (tracking.cpp:425) */
+#define VX_TRACK_BAD_ROTATION 4  /* non-finite R                            (tracking.cpp:441) */
+
+typedef struct {
+    int32_t status, n_matches, n_good_matches, n_pairs;
+    int32_t n_bad_index;        /* kept matches whose query / train index lies outside the two feature sets
+                                   (skipped, never read; the reference would index out of bounds) */
+    float min_distance;         /* min(100.0f, smallest distance), tracking.cpp:345-348 */
+    double parallax;            /* ComputeParallax(last_kf, curr, good matches) (tracking.cpp:548-560): the sum
+                                   over the kept matches with valid indices / n_good_matches; 0 when FEW_MATCHES */
+    vx_pnp_result pnp;          /* as vx_pnp_ransac on the gathered pairs (ok = 0 when the call returned early) */
+} vx_track_result;
+
+/* tracking.h:27-29 + tracking.cpp:420-423: 50 / 30 / {-1 (auto), 20, 2.0, 0.99, 0x5EED} */
+void vx_track_default_options(vx_track_options* o);
+/* Device pointer of a slot's vx_keypoint rows (their count: vx_orb_slot_device's d_count).  &kp[0].x
+ * with a stride of sizeof(vx_keypoint) = 20 bytes is a valid d_curr_xy below. */
+int vx_orb_slot_keypoints(vx_ctx* ctx, int slot, const vx_keypoint** d_kp);
+/* <- tracking.cpp:342-423, :449.  last_kf_id: a live keyframe of `map` (the query side of the matches;
+ * VX_ERR_INVALID otherwise).  Current frame positions: row i = two floats at d_curr_xy + i *
+ * curr_stride_bytes (20 for a slot's vx_keypoint rows, 8 for packed float2), *d_n_curr rows (device).
+ * d_matches / d_n_matches: a device match list of at most cap_matches entries; d_matches == NULL: the
+ * result of ctx's last vx_match_slots_async / vx_match_device_async (cap_matches ignored; VX_ERR_STATE
+ * if nothing was matched).  intr4 (host): fx fy cx cy of the current frame, non-zero focal lengths;
+ * opt->pnp.max_iterations <= 4096.  Enqueued on ctx's stream, which first waits (vx_stream_wait_ctx)
+ * for the map context's stream when ctx is another context; no host synchronisation.  Uses buffers of
+ * its own: vx_pnp_ransac / vx_essential_ransac may run before the fetch.
+ * The ordering is one way: nothing makes a later edit of `map` (vx_dmap_*, a LocalBA write-back, a
+ * call that grows its arrays or its id table) wait for this call's kernels on another context, so
+ * fetch — or order the map's context after ctx with vx_stream_wait_ctx — before editing the map.
+ * The call also brings the map's landmark id table up to date (host-side bookkeeping of the map
+ * included), so, like every vx_dmap_* call, it must not run concurrently with another call on the
+ * same map from another thread. */
+int vx_track_pnp_async(vx_ctx* ctx, vx_dmap* map, uint64_t last_kf_id,
+                       const float* d_curr_xy, int64_t curr_stride_bytes, const int32_t* d_n_curr,
+                       const vx_match* d_matches, const int32_t* d_n_matches, int cap_matches,
+                       const double* intr4, const vx_track_options* opt);
+/* One device-to-host copy (result | pair_match | inlier_mask) and one synchronisation; `status` is
+ * then set from the counts in the order of tracking.cpp:357, :402, :425, :441.  pair_match[k] = index
+ * in the match list of pair k (ascending), inlier_mask[k] = solvePnPRansac's inlier flag of pair k;
+ * either may be NULL.  VX_ERR_CAPACITY (with *out filled) if an array is given and n_pairs > cap_pairs. */
+int vx_track_pnp_fetch(vx_ctx* ctx, vx_track_result* out, int32_t* pair_match, uint8_t* inlier_mask,
+                       int cap_pairs);
+/* Host-input form (what visionx::PnPTracker calls): the last keyframe's and the current frame's
+ * descriptor rows (32 B each) and the current frame's positions (n_train float2) are staged and
+ * uploaded in ONE copy, matched on the device as vx_match_knn2_ratio would (query = last keyframe,
+ * `ratio`), and the match list goes straight into vx_track_pnp_async.  Completed by
+ * vx_track_pnp_fetch; the matches themselves by vx_match_fetch, if wanted.  "async" as in: nothing
+ * is waited for after the enqueue; the call may block at its start until the PREVIOUS call's upload
+ * has left the pinned staging block it reuses (it has, once that call was fetched). */
+int vx_track_pnp_host_async(vx_ctx* ctx, vx_dmap* map, uint64_t last_kf_id, const uint8_t* query_desc, int n_query,
+                            const uint8_t* train_desc, int n_train, const float* curr_xy, float ratio,
+                            const double* intr4, const vx_track_options* opt);
+/* threads of the pair-gather workgroup (its compaction chunk; for tests of the chunk boundaries) */
+int vx_track_block(void);
 
 /* <- E = cv::findEssentialMat(pts_last, pts_curr, K, cv::RANSAC, 0.999, 1.0, mask);
  *    inliers = cv::recoverPose(E, pts_last, pts_curr, K, R, t, mask)

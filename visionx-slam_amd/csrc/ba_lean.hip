@@ -54,21 +54,14 @@
 #include "ba_common.hpp"
 #include "ba_plan.hpp"
 #include "dmap.hpp"
+#include "lm_hash.hpp"
 #include "sba_plan.hpp"
 
 namespace vx {
 namespace {
 
 constexpr int kT = 256;
-constexpr uint64_t kEmptyKey = ~0ull;
 inline unsigned grid(long long n) { return (unsigned)std::max(1ll, (n + kT - 1) / kT); }
-
-__device__ __forceinline__ uint64_t mix(uint64_t x) {  // splitmix64
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 // ---------------------------------------------------------------- landmark id table (resident)
 __global__ void k_ht_clear(uint64_t* key, unsigned cap) {
@@ -92,16 +85,7 @@ __global__ void k_ht_add(uint64_t* key, int* val, unsigned mask, const uint64_t*
         h = (h + 1) & mask;
     }
 }
-__device__ __forceinline__ int ht_get(const uint64_t* key, const int* val, unsigned mask, uint64_t k) {
-    unsigned h = (unsigned)mix(k) & mask;
-    for (unsigned probe = 0; probe <= mask; ++probe) {
-        const uint64_t x = key[h];
-        if (x == k) return val[h];
-        if (x == kEmptyKey) return -1;
-        h = (h + 1) & mask;
-    }
-    return -1;
-}
+// (ht_get, the lookup, is in lm_hash.hpp)
 
 // ---------------------------------------------------------------- build kernels
 struct LeanArgs {
@@ -389,6 +373,8 @@ int scan_ex(vx_ctx* c, DevBuf& tmp, const T* in, T* out, int64_t n) {  // n + 1 
     return VX_OK;
 }
 
+}  // namespace
+
 // the resident id table covers rows [0, n_lm): new rows added, rebuilt when it has to grow
 int ht_sync(vx_ctx* c, vx_dmap* m) {
     const int64_t nl = m->n_lm;
@@ -412,8 +398,6 @@ int ht_sync(vx_ctx* c, vx_dmap* m) {
     m->ht_rows = nl;
     return VX_OK;
 }
-
-}  // namespace
 
 // What a lean build needs to know about the window before launching anything (host mirrors only)
 struct LeanCore {

@@ -453,7 +453,7 @@ int vx_match_device_async(vx_ctx* c, const uint8_t* dq, const int32_t* dnq, int 
     uint32_t rbits;
     std::memcpy(&rbits, &ratio, 4);
     // the buffers match_enqueue bakes into the graph are part of the key (they grow on demand)
-    return graph_run(c, {2, (uint64_t)(uintptr_t)dq, (uint64_t)(uintptr_t)dnq, (uint64_t)q_cap, (uint64_t)(uintptr_t)dt,
+    const int rc = graph_run(c, {2, (uint64_t)(uintptr_t)dq, (uint64_t)(uintptr_t)dnq, (uint64_t)q_cap, (uint64_t)(uintptr_t)dt,
                          (uint64_t)(uintptr_t)dnt, (uint64_t)t_cap, rbits, (uint64_t)(uintptr_t)c->partial.p,
                          (uint64_t)(uintptr_t)c->matches.p, (uint64_t)(uintptr_t)c->match_count.p},
                      [](vx_ctx* cc, void* v) {
@@ -462,6 +462,13 @@ int vx_match_device_async(vx_ctx* c, const uint8_t* dq, const int32_t* dnq, int 
                                               x->ratio);
                      },
                      &a);
+    // a replayed graph does not pass through match_enqueue: the host-side description of what
+    // c->matches now holds (read by vx_match_fetch's callers and vx_track_pnp_async) is set here
+    if (rc == VX_OK) {
+        c->match_cap = q_cap;
+        c->match_valid = true;
+    }
+    return rc;
 }
 
 int vx_match_fetch(vx_ctx* c, vx_match* out, int cap, int* n_out) {

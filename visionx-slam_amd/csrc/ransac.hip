@@ -367,7 +367,7 @@ __device__ __forceinline__ void block_count(int flag, int* lds_cnt) {
 __global__ void __launch_bounds__(kThreads) k_pnp_hyp(PnpArgs a) {
     const int p = blockIdx.y, h = blockIdx.x;
     const vx_pnp_options o = a.opt[p];
-    const int H = min(max(o.max_iterations, 0), kMaxHyp);
+    const int H = min(min(max(o.max_iterations, 0), kMaxHyp), a.hmax);  // (hmax: grid x and record stride)
     if (h >= H) return;
     const int b = a.offsets[p], n = a.offsets[p + 1] - b;
     const float* obj = a.obj + 3 * (size_t)b;
@@ -544,7 +544,7 @@ __device__ int3 replay(const HypRec* rec, int H, int n, double confidence) {
 __global__ void __launch_bounds__(kRefineThreads) k_pnp_refine(PnpArgs a) {
     const int p = blockIdx.x;
     const vx_pnp_options o = a.opt[p];
-    const int H = min(max(o.max_iterations, 0), kMaxHyp);
+    const int H = min(min(max(o.max_iterations, 0), kMaxHyp), a.hmax);  // (hmax: grid x and record stride)
     const int b = a.offsets[p], n = a.offsets[p + 1] - b;
     const float* obj = a.obj + 3 * (size_t)b;
     const float* img = a.img + 2 * (size_t)b;
@@ -669,6 +669,24 @@ __global__ void __launch_bounds__(kRefineThreads) k_pnp_refine(PnpArgs a) {
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
+
+int pnp_enqueue(vx_ctx* c, int P, int hmax, const PnpDeviceArgs& d, DevBuf& hyp) {
+    VX_HIP(c, hyp.ensure((size_t)P * hmax * sizeof(HypRec)));
+    PnpArgs a{};
+    a.offsets = d.offsets;
+    a.intr = d.intr;
+    a.opt = d.opt;
+    a.obj = d.obj;
+    a.img = d.img;
+    a.hyp = hyp.as<HypRec>();
+    a.hmax = hmax;
+    a.out = d.out;
+    a.mask = d.mask;
+    VX_HIP(c, launch(c, kStPnpHyp, k_pnp_hyp, dim3(hmax, P), dim3(kThreads), 0, c->stream, a));
+    VX_HIP(c, launch(c, kStPnpRefine, k_pnp_refine, dim3(P), dim3(kRefineThreads), 0, c->stream, a));
+    return VX_OK;
+}
+
 }  // namespace vx
 
 using namespace vx;
@@ -723,22 +741,18 @@ int vx_pnp_ransac_batch(vx_ctx* c, int P, const int32_t* offsets, const float* o
     }
     VX_HIP(c, c->rs_in.ensure(in_bytes));
     VX_HIP(c, hipMemcpyAsync(c->rs_in.p, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, c->rs_hyp.ensure((size_t)P * hmax * sizeof(HypRec)));
     const size_t out_bytes = align16((size_t)P * sizeof(vx_pnp_result)) + (size_t)std::max<int64_t>(N, 1);
     VX_HIP(c, c->rs_out.ensure(out_bytes));
     uint8_t* din = c->rs_in.as<uint8_t>();
-    PnpArgs a{};
+    PnpDeviceArgs a{};
     a.offsets = reinterpret_cast<const int*>(din + o_off);
     a.intr = reinterpret_cast<const double*>(din + o_intr);
     a.opt = reinterpret_cast<const vx_pnp_options*>(din + o_opt);
     a.obj = reinterpret_cast<const float*>(din + o_obj);
     a.img = reinterpret_cast<const float*>(din + o_img);
-    a.hyp = c->rs_hyp.as<HypRec>();
-    a.hmax = hmax;
     a.out = c->rs_out.as<vx_pnp_result>();
     a.mask = c->rs_out.as<uint8_t>() + align16((size_t)P * sizeof(vx_pnp_result));
-    VX_HIP(c, launch(c, kStPnpHyp, k_pnp_hyp, dim3(hmax, P), dim3(kThreads), 0, c->stream, a));
-    VX_HIP(c, launch(c, kStPnpRefine, k_pnp_refine, dim3(P), dim3(kRefineThreads), 0, c->stream, a));
+    if (int rc = pnp_enqueue(c, P, hmax, a, c->rs_hyp)) return rc;
     VX_HIP(c, c->rs_host_out.ensure(out_bytes));
     VX_HIP(c, hipMemcpyAsync(c->rs_host_out.p, c->rs_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     VX_HIP(c, hipStreamSynchronize(c->stream));

@@ -1,0 +1,447 @@
+// track.hip — Tracking::TrackWithPnP (core/frontend/tracking.cpp:332-455) from the match list to the
+// pose without leaving the device (vx_track_pnp_async / vx_track_pnp_fetch).
+//
+// The reference filters the matches by distance (:342-355), builds the 3D-2D pairs with one
+// Map::GetLandmark per match (:364-400), calls cv::solvePnPRansac on them (:414-423) and averages
+// the pixel displacement of the kept matches (ComputeParallax, :449, :548-560).  Everything those
+// steps read is already resident: the match list (match.hip), the current frame's keypoints (an
+// extraction slot), the last keyframe's features and the landmarks (vx_dmap), the landmark id ->
+// row table (lm_hash.hpp).  One kernel turns them into the device-side problem record the RANSAC
+// kernels of ransac.hip read (their correspondence count included), so the sequence is
+//
+//   k_track_pairs (1 workgroup)  ->  k_pnp_hyp (H, 1)  ->  k_pnp_refine (1)     [pnp_enqueue]
+//
+// with no host step between and one synchronisation, in the fetch.
+//
+// k_track_pairs is ONE workgroup: the problem is the match list of one frame pair (at most a few
+// thousand entries) and both compactions are ordered (the pairs keep the match order, which is
+// what fixes RANSAC's sample stream), so each needs a block-wide exclusive scan; a second
+// workgroup would need a second launch or a grid barrier to see the first one's totals.  Its stages:
+//   1  min distance       strided loads, wave butterfly + LDS, started at 100.0f (:345-348)
+//   2  thr = max(2 min, 30)
+//   3  distance filter    match i kept when distance <= thr; kept indices written in match order:
+//                         per chunk of kBlock matches a wave64 ballot + mbcnt gives the rank inside
+//                         the wave, the wave totals are scanned in LDS, a running base carries over
+//   4  pair gather        kept match j (in order): index bounds, feature flags, hash probe, lm_bad,
+//                         position checks (:373-394); survivors compacted the same way into
+//                         obj (float3), img (float2), pair_match
+//   5  parallax           per-thread partial over its kept matches (j = t, t + kBlock, ...), wave
+//                         butterfly, wave partials summed in wave order: a fixed order, so the
+//                         double result repeats bit for bit
+//   6  problem record     offsets {0, n_pairs} (or {0, 0} when a gate of :357 / :402 fails: the RANSAC
+//                         kernels then return ok = 0 without a hypothesis), intrinsics, options with
+//                         max_iterations resolved (:421)
+// No atomics anywhere: every output position comes from a scan.
+//
+// Block size 1024 (16 waves, 4 per SIMD): the kernel is a chain of dependent global loads per
+// match (match -> feature -> hash slot -> lm_bad / lm_pos) on a single CU, so what bounds it is
+// how many of those chains are in flight; 1024 threads put a typical 1000-2000 match list through
+// each stage in one or two chunks (two __syncthreads per chunk).  Registers are no constraint
+// (58 VGPRs, no scratch); LDS: 16 wave counts + 16 wave minima + 16 wave doubles = 256 B.
+// The hash probe and the lm_bad / lm_pos reads behind it are the only loads whose address depends
+// on another load of the same stage beyond the match record itself.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "vx_internal.hpp"
+#include "dmap.hpp"
+#include "lm_hash.hpp"
+
+namespace vx {
+namespace {
+
+constexpr int kBlock = 1024;
+constexpr int kWaves = kBlock / 64;
+
+struct TrackArgs {
+    // match list (query = last keyframe feature, train = current frame feature)
+    const vx_match* matches;
+    const int* n_matches;
+    int cap_matches;
+    // current frame positions: two floats at curr_xy + i * stride
+    const uint8_t* curr_xy;
+    int64_t stride;
+    const int* n_curr;
+    // last keyframe: resident feature rows [f0, f0 + nf)
+    int64_t f0;
+    int nf;
+    const double* feat_uv;
+    const uint64_t* feat_lm;
+    const uint8_t* feat_fl;
+    // landmarks
+    const uint64_t* ht_key;
+    const int* ht_val;
+    unsigned ht_mask;
+    const uint8_t* lm_bad;
+    const double* lm_pos;
+    // options
+    int min_matches, min_inliers;
+    vx_pnp_options pnp;
+    double intr[4];
+    // scratch + outputs
+    int* good;              // cap_matches: kept match indices, match order
+    float* obj;             // 3 per pair
+    float* img;             // 2 per pair
+    int* pair_match;        // per pair
+    uint8_t* mask;          // per pair (zeroed here, written by k_pnp_refine)
+    vx_track_result* res;
+    int* offsets;           // 2
+    double* intr_out;       // 4
+    vx_pnp_options* opt_out;
+};
+
+// Exclusive rank of this thread's flag among the block's flags (thread order) and their total.
+// Two barriers: the wave counts are read by everyone before the next call rewrites them.
+__device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t b = __ballot(flag);
+    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    if (lane == 0) s_cnt[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        const int v = s_cnt[w];
+        before += w < wave ? v : 0;
+        all += v;
+    }
+    __syncthreads();
+    *total = all;
+    return before + in_wave;
+}
+
+__device__ __forceinline__ void curr_pos(const TrackArgs& a, int i, float* x, float* y) {
+    const float* p = reinterpret_cast<const float*>(a.curr_xy + (int64_t)i * a.stride);
+    *x = p[0];
+    *y = p[1];
+}
+
+__global__ void __launch_bounds__(kBlock) k_track_pairs(TrackArgs a) {
+    __shared__ int s_cnt[kWaves];
+    __shared__ float s_min[kWaves];
+    __shared__ double s_sum[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(*a.n_matches, 0), a.cap_matches);
+    const int n_curr = *a.n_curr;
+
+    // 1: min distance (tracking.cpp:345-348)
+    float mn = 100.0f;
+    for (int i = tid; i < n; i += kBlock) {
+        const float d = a.matches[i].distance;
+        if (d < mn) mn = d;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float o = __shfl_xor(mn, off);
+        if (o < mn) mn = o;
+    }
+    if (lane == 0) s_min[wave] = mn;
+    __syncthreads();
+    mn = s_min[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w)
+        if (s_min[w] < mn) mn = s_min[w];
+    // 2: std::max(2 * min_dist, 30.0f) (:350)
+    const float thr = fmaxf(2 * mn, 30.0f);
+
+    // 3: the kept matches, in match order
+    int n_good = 0;
+    for (int base = 0; base < n; base += kBlock) {
+        const int i = base + tid;
+        const bool keep = i < n && a.matches[i].distance <= thr;
+        int total;
+        const int r = block_rank(keep, s_cnt, &total);
+        if (keep) a.good[n_good + r] = i;
+        n_good += total;
+    }
+    __syncthreads();  // a.good is read by other threads below (one workgroup: one CU, one L1)
+
+    // 4 + 5: pairs in kept-match order, parallax partials
+    const bool enough = n_good >= a.min_matches;
+    int n_pairs = 0, n_bad = 0;
+    double part = 0.0;
+    for (int base = 0; base < n_good; base += kBlock) {
+        const int j = base + tid;
+        bool pair = false, bad_index = false;
+        int mi = 0;
+        float ox = 0.f, oy = 0.f, oz = 0.f, ix = 0.f, iy = 0.f;
+        if (j < n_good) {
+            mi = a.good[j];
+            const vx_match m = a.matches[mi];
+            if (m.query_idx < 0 || m.query_idx >= a.nf || m.train_idx < 0 || m.train_idx >= n_curr) {
+                bad_index = true;
+            } else {
+                const int64_t f = a.f0 + m.query_idx;
+                curr_pos(a, m.train_idx, &ix, &iy);
+                if (enough) {  // ComputeParallax (:548-560): (p1 - p2).norm() in double
+                    const double dx = a.feat_uv[2 * f] - (double)ix;
+                    const double dy = a.feat_uv[2 * f + 1] - (double)iy;
+                    part += sqrt(dx * dx + dy * dy);
+                }
+                const uint8_t fl = a.feat_fl[f];
+                if ((fl & 1) && !(fl & 2)) {  // has_landmark && !is_outlier (:375)
+                    const int row = ht_get(a.ht_key, a.ht_val, a.ht_mask, a.feat_lm[f]);  // GetLandmark (:378)
+                    if (row >= 0 && a.lm_bad[row] == 0) {                                  // !lm, IsBad (:379-384)
+                        const double px = a.lm_pos[3 * (int64_t)row], py = a.lm_pos[3 * (int64_t)row + 1],
+                                     pz = a.lm_pos[3 * (int64_t)row + 2];
+                        const bool nan = px != px || py != py || pz != pz;              // (:388)
+                        const bool far = fabs(px) > 1000 || fabs(py) > 1000 || fabs(pz) > 1000;  // (:391)
+                        if (!nan && !far) {
+                            pair = true;
+                            ox = (float)px;  // cv::Point3f (:395)
+                            oy = (float)py;
+                            oz = (float)pz;
+                        }
+                    }
+                }
+            }
+        }
+        int total;
+        const int r = block_rank(pair, s_cnt, &total);
+        if (pair) {
+            const int k = n_pairs + r;
+            a.obj[3 * k] = ox;
+            a.obj[3 * k + 1] = oy;
+            a.obj[3 * k + 2] = oz;
+            a.img[2 * k] = ix;
+            a.img[2 * k + 1] = iy;
+            a.pair_match[k] = mi;
+            a.mask[k] = 0;
+        }
+        n_pairs += total;
+        n_bad += bad_index ? 1 : 0;
+    }
+
+    // 5: parallax (and the skipped-index count), fixed order
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        part += __shfl_xor(part, off);
+        n_bad += __shfl_xor(n_bad, off);
+    }
+    if (lane == 0) {
+        s_sum[wave] = part;
+        s_cnt[wave] = n_bad;
+    }
+    __syncthreads();
+
+    // 6: result counts and the PnP problem record
+    if (tid == 0) {
+        double sum = s_sum[0];
+        n_bad = s_cnt[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) {
+            sum += s_sum[w];
+            n_bad += s_cnt[w];
+        }
+        vx_track_result* r = a.res;
+        r->status = 0;
+        r->n_matches = n;
+        r->n_good_matches = n_good;
+        r->n_pairs = n_pairs;
+        r->n_bad_index = n_bad;
+        r->min_distance = mn;
+        r->parallax = enough && n_good > 0 ? sum / (double)n_good : 0.0;  // cnt > 0 ? sum / cnt : 0 (:559)
+        const bool run = enough && n_pairs >= a.min_inliers;
+        a.offsets[0] = 0;
+        a.offsets[1] = run ? n_pairs : 0;
+        for (int k = 0; k < 4; ++k) a.intr_out[k] = a.intr[k];
+        vx_pnp_options o = a.pnp;
+        if (o.max_iterations < 0) o.max_iterations = min(100, 2 * n_pairs);  // (:421)
+        *a.opt_out = o;
+    }
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// packed result block: vx_track_result | pair_match[cap] | mask[cap]
+size_t off_pair_match() { return align16(sizeof(vx_track_result)); }
+size_t off_mask(int cap) { return off_pair_match() + align16((size_t)cap * sizeof(int32_t)); }
+size_t packed_bytes(int cap) { return off_mask(cap) + align16((size_t)cap); }
+
+}  // namespace
+}  // namespace vx
+
+using namespace vx;
+
+extern "C" {
+
+void vx_track_default_options(vx_track_options* o) {
+    if (!o) return;
+    o->min_matches = 50;  // Tracking::Options (tracking.h:27-28)
+    o->min_inliers = 30;
+    vx_pnp_default_options(0, &o->pnp);
+    o->pnp.max_iterations = -1;  // min(100, 2 * n_pairs) once n_pairs is known (tracking.cpp:421)
+}
+
+int vx_track_block(void) { return kBlock; }
+
+int vx_orb_slot_keypoints(vx_ctx* c, int slot, const vx_keypoint** d_kp) {
+    if (!c || !d_kp) return VX_ERR_INVALID;
+    if (slot < 0 || slot >= VX_MAX_SLOTS || !c->slots[slot].valid)
+        return set_error(c, VX_ERR_STATE, "slot %d holds no extraction", slot);
+    *d_kp = c->slots[slot].kp.as<vx_keypoint>();
+    return VX_OK;
+}
+
+int vx_track_pnp_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const float* d_curr_xy, int64_t curr_stride_bytes,
+                       const int32_t* d_n_curr, const vx_match* d_matches, const int32_t* d_n_matches, int cap_matches,
+                       const double* intr4, const vx_track_options* opt) {
+    if (!c) return VX_ERR_INVALID;
+    if (!m || !m->c || !d_curr_xy || !d_n_curr || !intr4 || !opt)
+        return set_error(c, VX_ERR_INVALID, "vx_track_pnp_async: null argument");
+    if (curr_stride_bytes < 8 || (curr_stride_bytes & 3))
+        return set_error(c, VX_ERR_INVALID, "position stride %lld: a multiple of 4, at least 8", (long long)curr_stride_bytes);
+    if (m->c->device != c->device) return set_error(c, VX_ERR_INVALID, "map and context on different devices");
+    if (d_matches) {
+        if (!d_n_matches || cap_matches < 0) return set_error(c, VX_ERR_INVALID, "match list without a count / capacity");
+    } else {
+        if (!c->match_valid) return set_error(c, VX_ERR_STATE, "no match enqueued on this context");
+        d_matches = c->matches.as<vx_match>();
+        d_n_matches = c->match_count.as<int32_t>();
+        cap_matches = c->match_cap;
+    }
+    const auto kf = m->kf_index.find(last_kf_id);
+    if (kf == m->kf_index.end())
+        return set_error(c, VX_ERR_INVALID, "keyframe %llu is not in the map", (unsigned long long)last_kf_id);
+    if (!(intr4[0] != 0.0 && intr4[1] != 0.0)) return set_error(c, VX_ERR_INVALID, "zero focal length");
+    if (opt->pnp.max_iterations > 4096)
+        return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", opt->pnp.max_iterations);
+    if (opt->pnp.refine_iterations < 0 || !(opt->pnp.reproj_error >= 0.0))
+        return set_error(c, VX_ERR_INVALID, "bad PnP options");
+    VX_HIP(c, hipSetDevice(c->device));
+    // the id table must hold the landmarks added since the last LocalBA; it belongs to the map, so it
+    // is brought up to date on the map context's stream, which this context's stream then follows
+    int rc;
+    if ((rc = ht_sync(m->c, m))) return set_error(c, rc, "landmark id table: %s", vx_last_error(m->c));
+    if ((rc = vx_stream_wait_ctx(c, m->c))) return rc;
+
+    const int cap = std::max(cap_matches, 1);
+    VX_HIP(c, c->tk_good.ensure((size_t)cap * sizeof(int)));
+    VX_HIP(c, c->tk_obj.ensure((size_t)cap * 3 * sizeof(float)));
+    VX_HIP(c, c->tk_img.ensure((size_t)cap * 2 * sizeof(float)));
+    VX_HIP(c, c->tk_prob.ensure(16 + 4 * sizeof(double) + sizeof(vx_pnp_options)));
+    VX_HIP(c, c->tk_out.ensure(packed_bytes(cap)));
+    uint8_t* prob = c->tk_prob.as<uint8_t>();
+    uint8_t* out = c->tk_out.as<uint8_t>();
+    const int k = kf->second;
+    TrackArgs a{};
+    a.matches = d_matches;
+    a.n_matches = d_n_matches;
+    a.cap_matches = cap_matches;
+    a.curr_xy = reinterpret_cast<const uint8_t*>(d_curr_xy);
+    a.stride = curr_stride_bytes;
+    a.n_curr = d_n_curr;
+    a.f0 = m->kf_feat_ptr[k];
+    a.nf = (int)(m->kf_feat_ptr[k + 1] - m->kf_feat_ptr[k]);
+    a.feat_uv = m->feat_uv.as<double>();
+    a.feat_lm = m->feat_lm.as<uint64_t>();
+    a.feat_fl = m->feat_fl.as<uint8_t>();
+    a.ht_key = m->ht_key.as<uint64_t>();
+    a.ht_val = m->ht_val.as<int>();
+    a.ht_mask = m->ht_cap - 1;
+    a.lm_bad = m->lm_bad.as<uint8_t>();
+    a.lm_pos = m->lm_pos.as<double>();
+    a.min_matches = opt->min_matches;
+    a.min_inliers = opt->min_inliers;
+    a.pnp = opt->pnp;
+    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+    a.good = c->tk_good.as<int>();
+    a.obj = c->tk_obj.as<float>();
+    a.img = c->tk_img.as<float>();
+    a.pair_match = reinterpret_cast<int*>(out + off_pair_match());
+    a.mask = out + off_mask(cap);
+    a.res = reinterpret_cast<vx_track_result*>(out);
+    a.offsets = reinterpret_cast<int*>(prob);
+    a.intr_out = reinterpret_cast<double*>(prob + 16);
+    a.opt_out = reinterpret_cast<vx_pnp_options*>(prob + 16 + 4 * sizeof(double));
+    c->tk_valid = false;
+    VX_HIP(c, launch(c, kStTrackPairs, k_track_pairs, dim3(1), dim3(kBlock), 0, c->stream, a));
+    PnpDeviceArgs d{};
+    d.offsets = a.offsets;
+    d.intr = a.intr_out;
+    d.opt = a.opt_out;
+    d.obj = a.obj;
+    d.img = a.img;
+    d.out = &a.res->pnp;
+    d.mask = a.mask;
+    // the hypothesis grid is the host-side bound of the budget; k_pnp_hyp exits beyond the resolved one
+    const int hmax = std::max(1, opt->pnp.max_iterations < 0 ? 100 : opt->pnp.max_iterations);
+    if ((rc = pnp_enqueue(c, 1, hmax, d, c->tk_hyp))) return rc;
+    c->tk_cap = cap;
+    c->tk_min_matches = opt->min_matches;
+    c->tk_min_inliers = opt->min_inliers;
+    c->tk_valid = true;
+    return VX_OK;
+}
+
+int vx_track_pnp_host_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const uint8_t* query_desc, int n_query,
+                            const uint8_t* train_desc, int n_train, const float* curr_xy, float ratio,
+                            const double* intr4, const vx_track_options* opt) {
+    if (!c) return VX_ERR_INVALID;
+    if (n_query < 0 || n_train < 0 || (n_query && !query_desc) || (n_train && (!train_desc || !curr_xy)))
+        return set_error(c, VX_ERR_INVALID, "vx_track_pnp_host_async: bad descriptor / position arguments");
+    VX_HIP(c, hipSetDevice(c->device));
+    // one staged block: {n_query, n_train} | query rows | train rows | positions.  The row capacities
+    // (what the match is enqueued with; the counts are read on the device) are rounded up to 256 so
+    // frames with about as many features share one launch configuration (its captured graph).
+    const int cap_q = (std::max(n_query, 1) + 255) & ~255, cap_t = (std::max(n_train, 1) + 255) & ~255;
+    const size_t o_q = 16, o_t = o_q + (size_t)cap_q * 32, o_xy = o_t + (size_t)cap_t * 32,
+                 bytes = o_xy + (size_t)cap_t * 8;
+    // (the one place this entry can block: until the previous call's upload has left the staging)
+    if (c->tk_in_event) VX_HIP(c, hipEventSynchronize(c->tk_in_event));
+    else VX_HIP(c, hipEventCreateWithFlags(&c->tk_in_event, hipEventDisableTiming));
+    VX_HIP(c, c->tk_in_host.ensure(bytes));
+    VX_HIP(c, c->tk_in.ensure(bytes));
+    uint8_t* h = static_cast<uint8_t*>(c->tk_in_host.p);
+    const int32_t counts[4] = {n_query, n_train, 0, 0};
+    std::memcpy(h, counts, sizeof counts);
+    // rows between the counts and the rounded capacities are not filled: the match kernels stop at
+    // the device-side counts, so what the upload carries there is never read
+    if (n_query) std::memcpy(h + o_q, query_desc, (size_t)n_query * 32);
+    if (n_train) {
+        std::memcpy(h + o_t, train_desc, (size_t)n_train * 32);
+        std::memcpy(h + o_xy, curr_xy, (size_t)n_train * 8);
+    }
+    VX_HIP(c, hipMemcpyAsync(c->tk_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
+    VX_HIP(c, hipEventRecord(c->tk_in_event, c->stream));
+    const uint8_t* d = c->tk_in.as<uint8_t>();
+    const int32_t* dn = c->tk_in.as<int32_t>();
+    int rc;
+    if ((rc = vx_match_device_async(c, d + o_q, dn, cap_q, d + o_t, dn + 1, cap_t, ratio))) return rc;
+    // the list just enqueued, named explicitly with the capacity it was enqueued with
+    return vx_track_pnp_async(c, m, last_kf_id, reinterpret_cast<const float*>(d + o_xy), 8, dn + 1,
+                              c->matches.as<vx_match>(), c->match_count.as<int32_t>(), cap_q, intr4, opt);
+}
+
+int vx_track_pnp_fetch(vx_ctx* c, vx_track_result* out, int32_t* pair_match, uint8_t* inlier_mask, int cap_pairs) {
+    if (!c || !out) return c ? set_error(c, VX_ERR_INVALID, "vx_track_pnp_fetch: null result") : VX_ERR_INVALID;
+    if (!c->tk_valid) return set_error(c, VX_ERR_STATE, "no vx_track_pnp_async enqueued");
+    VX_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = packed_bytes(c->tk_cap);
+    VX_HIP(c, c->tk_host.ensure(bytes));
+    VX_HIP(c, hipMemcpyAsync(c->tk_host.p, c->tk_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) prof_collect(c);
+    const uint8_t* h = static_cast<const uint8_t*>(c->tk_host.p);
+    std::memcpy(out, h, sizeof *out);
+    bool finite = true;  // R = Rodrigues(rvec) is finite exactly when the pose is (tracking.cpp:441)
+    for (int k = 0; k < 7; ++k) finite &= std::isfinite(out->pnp.pose[k]);
+    if (out->n_good_matches < c->tk_min_matches) out->status = VX_TRACK_FEW_MATCHES;
+    else if (out->n_pairs < c->tk_min_inliers) out->status = VX_TRACK_FEW_PAIRS;
+    else if (!out->pnp.ok || out->pnp.n_inliers < c->tk_min_inliers) out->status = VX_TRACK_PNP_FAILED;
+    else if (!finite) out->status = VX_TRACK_BAD_ROTATION;
+    else out->status = VX_TRACK_OK;
+    const int np = out->n_pairs;
+    if ((pair_match || inlier_mask) && np > cap_pairs)
+        return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
+    if (pair_match && np) std::memcpy(pair_match, h + off_pair_match(), (size_t)np * sizeof(int32_t));
+    if (inlier_mask && np) std::memcpy(inlier_mask, h + off_mask(c->tk_cap), (size_t)np);
+    return VX_OK;
+}
+
+}  // extern "C"
+
+static_assert(sizeof(vx_track_options) == 40, "vx_track_options layout (python TRACK_OPTIONS_DTYPE)");
+static_assert(sizeof(vx_track_result) == 176, "vx_track_result layout (python TRACK_RESULT_DTYPE)");
+static_assert(sizeof(vx_keypoint) == 20, "vx_keypoint rows as a position array of stride 20");

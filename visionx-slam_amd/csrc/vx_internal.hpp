@@ -66,6 +66,7 @@ enum Stage : int {
     kStBaIter,        // fused LocalBA iteration (k_ba_iter)
     kStBaPrologue,    // iteration 0's pose stage of the fused path
     kStBaWin,         // the whole LocalBA window in one persistent launch (k_ba_win)
+    kStTrackPairs,    // TrackWithPnP's filter + pair gather (k_track_pairs)
     kStCount
 };
 
@@ -221,6 +222,17 @@ struct vx_ctx {
     vx::PinnedBuf rs_host, rs_host_out;
     vx::DevBuf rs_in, rs_hyp, rs_out;  // (shared by vx_essential_ransac, essential.hip)
 
+    // ---- TrackWithPnP on the device (track.hip): buffers of its own, so the RANSAC entry points
+    // above may run between vx_track_pnp_async and its fetch
+    vx::DevBuf tk_good, tk_obj, tk_img, tk_prob, tk_hyp, tk_out;  // kept-match list, pairs, PnP record, packed result
+    vx::PinnedBuf tk_host;
+    vx::PinnedBuf tk_in_host;    // vx_track_pnp_host_async: descriptors + positions staged for one upload ...
+    vx::DevBuf tk_in;            // ... into one device block
+    hipEvent_t tk_in_event = nullptr;  // (recorded after that upload: the staging is reused once it has passed)
+    int tk_cap = 0;              // match capacity of the enqueued call (sizes the packed result)
+    int tk_min_matches = 0, tk_min_inliers = 0;
+    bool tk_valid = false;
+
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {
         vx::DevBuf wptr, wlm, wfl, cam, wid, wuv, lid, bad, optr, okf, ofi, pos, hkey, hval, f_lm, f_pv, f_first,
@@ -297,6 +309,23 @@ inline hipError_t launch(vx_ctx* c, int stage, F kernel, dim3 grid, dim3 block, 
 }
 
 int orb_prepare(vx_ctx* c, const vx_orb_params* p, int w, int h);
+
+// PnP RANSAC on problems already in device memory (ransac.hip): k_pnp_hyp over (hmax, P) and
+// k_pnp_refine over P enqueued on c->stream, nothing synchronised.  Problem p owns correspondences
+// [offsets[p], offsets[p + 1]) and runs min(opt[p].max_iterations, 4096, hmax) hypotheses (hmax is the
+// grid and the stride of the hypothesis records: the kernels clamp to it) — every input, the counts
+// included, is read on the device.  `hyp` is the hypothesis scratch (grown to P * hmax
+// records).  vx_pnp_ransac_batch and vx_track_pnp_async both end here.
+struct PnpDeviceArgs {
+    const int* offsets;           // P + 1
+    const double* intr;           // 4 per problem
+    const vx_pnp_options* opt;    // per problem
+    const float* obj;             // 3 per correspondence
+    const float* img;             // 2 per correspondence
+    vx_pnp_result* out;           // per problem
+    uint8_t* mask;                // per correspondence
+};
+int pnp_enqueue(vx_ctx* c, int P, int hmax, const PnpDeviceArgs& d, DevBuf& hyp);
 
 // Runs `enqueue` (which only enqueues work on c->stream) through the context's graph cache: the
 // first call with a key runs eagerly (so every buffer it needs gets allocated outside a capture),

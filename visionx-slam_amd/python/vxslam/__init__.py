@@ -96,6 +96,7 @@ EXPORTS = [
     "vx_orb_extract_batch_async", "vx_orb_batch_fetch", "vx_orb_batch_device", "vx_match_batch_async",
     "vx_match_batch_fetch", "vx_orb_extract_batch", "vx_match_knn2_ratio_batch", "vx_orb_set_order",
     "vx_orb_get_order", "vx_orb_set_debug", "vx_orb_debug_read", "vx_test_retain_best",
+    "vx_track_default_options", "vx_orb_slot_keypoints", "vx_track_pnp_async", "vx_track_pnp_fetch", "vx_track_block", "vx_track_pnp_host_async",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -177,6 +178,14 @@ def lib():
         L.vx_seq_length.argtypes = [C.c_void_p]
         L.vx_seq_run.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.vx_seq_set_threads.argtypes = [C.c_void_p, C.c_int]
+        L.vx_track_default_options.restype = None
+        L.vx_track_default_options.argtypes = [C.c_void_p]
+        L.vx_orb_slot_keypoints.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.vx_track_pnp_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.vx_track_pnp_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.vx_track_pnp_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.vx_ba_shard_of.restype = C.c_uint32
         L.vx_ba_shard_of.argtypes = [C.c_uint64, C.c_int]
         _lib = L
@@ -227,6 +236,35 @@ def pnp_options(n, max_iterations=None, reproj_error=2.0, confidence=0.99, seed=
     o["confidence"] = confidence
     o["seed"] = seed
     return o
+
+
+# vx_track_options / vx_track_result (include/vx_slam.h; sizes pinned in csrc/track.hip)
+TRACK_OPTIONS_DTYPE = np.dtype([("min_matches", "<i4"), ("min_inliers", "<i4"), ("pnp", PNP_OPTIONS_DTYPE)])
+TRACK_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_good_matches", "<i4"), ("n_pairs", "<i4"),
+                               ("n_bad_index", "<i4"), ("min_distance", "<f4"), ("parallax", "<f8"),
+                               ("pnp", PNP_RESULT_DTYPE)])
+TRACK_OK, TRACK_FEW_MATCHES, TRACK_FEW_PAIRS, TRACK_PNP_FAILED, TRACK_BAD_ROTATION = range(5)
+
+
+def track_options(min_matches=None, min_inliers=None, max_iterations=None, reproj_error=None, confidence=None,
+                  seed=None, refine_iterations=None):
+    """Tracking::Options + solvePnPRansac's arguments in Tracking::TrackWithPnP (tracking.h:27-29,
+    tracking.cpp:420-423); max_iterations -1 (the default) = min(100, 2 * pairs), resolved on the device."""
+    o = np.zeros((), TRACK_OPTIONS_DTYPE)
+    lib().vx_track_default_options(_p(o))
+    for k, v in (("min_matches", min_matches), ("min_inliers", min_inliers)):
+        if v is not None:
+            o[k] = v
+    for k, v in (("max_iterations", max_iterations), ("reproj_error", reproj_error), ("confidence", confidence),
+                 ("seed", seed), ("refine_iterations", refine_iterations)):
+        if v is not None:
+            o["pnp"][k] = v
+    return o
+
+
+def track_block() -> int:
+    """threads of the pair-gather workgroup (the chunk of its two compactions)"""
+    return int(lib().vx_track_block())
 
 
 def default_orb_params(n_features=1000, scale_factor=1.2, n_levels=8, fast_threshold=20,
@@ -439,6 +477,53 @@ class Context:
         d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
         self._check(lib().vx_orb_slot_device(self._h, slot, C.byref(d), C.byref(n), C.byref(cap)))
         return d.value, n.value, cap.value
+
+    def slot_keypoints(self, slot: int) -> int:
+        """device pointer of an extraction slot's KEYPOINT_DTYPE rows (their count: slot_device()[1])"""
+        d = C.c_void_p()
+        self._check(lib().vx_orb_slot_keypoints(self._h, slot, C.byref(d)))
+        return d.value
+
+    def track_pnp_async(self, dmap: "DMap", last_kf_id: int, curr, intr, opts=None, matches=None):
+        """Tracking::TrackWithPnP after the match (tracking.cpp:342-423, :449) on the device.  curr: an
+        extraction slot of this context, or (device pointer of the first x, row stride in bytes,
+        device pointer of the int32 row count); matches: None = this context's last match_*_async
+        result, or (device pointer of MATCH_DTYPE rows, device pointer of the int32 count, capacity).
+        Nothing synchronises; track_pnp_fetch() completes it."""
+        if isinstance(curr, (int, np.integer)):
+            curr = (self.slot_keypoints(int(curr)), KEYPOINT_DTYPE.itemsize, self.slot_device(int(curr))[1])
+        xy, stride, n_ptr = curr
+        m_ptr, mn_ptr, m_cap = matches if matches is not None else (None, None, 0)
+        intr = np.ascontiguousarray(intr, np.float64)
+        assert intr.size == 4
+        opts = np.ascontiguousarray(track_options() if opts is None else opts, TRACK_OPTIONS_DTYPE)
+        self._check(lib().vx_track_pnp_async(self._h, dmap.handle, int(last_kf_id), C.c_void_p(xy), int(stride),
+                                             C.c_void_p(n_ptr), C.c_void_p(m_ptr), C.c_void_p(mn_ptr), int(m_cap),
+                                             _p(intr), _p(opts)))
+
+    def track_pnp_host_async(self, dmap: "DMap", last_kf_id: int, desc_kf, desc_curr, curr_xy, intr, opts=None,
+                             ratio: float = 0.8):
+        """The host-input form (vx_track_pnp_host_async, what visionx::PnPTracker calls): both frames'
+        descriptor rows and the current positions uploaded in one copy, matched on the device, then
+        as track_pnp_async on that match list."""
+        q = np.ascontiguousarray(desc_kf, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(desc_curr, np.uint8).reshape(-1, 32)
+        xy = np.ascontiguousarray(curr_xy, np.float32).reshape(-1, 2)
+        assert len(xy) == len(t)
+        intr = np.ascontiguousarray(intr, np.float64)
+        opts = np.ascontiguousarray(track_options() if opts is None else opts, TRACK_OPTIONS_DTYPE)
+        self._check(lib().vx_track_pnp_host_async(self._h, dmap.handle, int(last_kf_id), _p(q), len(q), _p(t), len(t),
+                                                  _p(xy), ratio, _p(intr), _p(opts)))
+
+    def track_pnp_fetch(self, cap: int = 8192):
+        """(TRACK_RESULT_DTYPE record, pair_match int32[n_pairs], inlier mask uint8[n_pairs]) of the last
+        track_pnp_async: one copy, one synchronisation."""
+        out = np.zeros(1, TRACK_RESULT_DTYPE)
+        pm = np.zeros(max(cap, 1), np.int32)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        self._check(lib().vx_track_pnp_fetch(self._h, _p(out), _p(pm), _p(mask), cap))
+        n = int(out[0]["n_pairs"])
+        return out[0], pm[:n].copy(), mask[:n].copy()
 
     def match_device_async(self, query, train, ratio: float = 0.8):
         """Match device descriptor sets given as slot_device() triples (possibly of another context)."""

@@ -372,14 +372,9 @@ def make_keyframe_pair(seed: int, n: int = 2000, *, width: int = 640, height: in
             "depth": np.ascontiguousarray(depth), "pw_true": pw, "inv": inv}
 
 
-def make_pnp_problem(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noise_px: float = 0.5,
-                     width: int = 640, height: int = 480, intr=(FX, FY, CX, CY), z_range=(1.0, 6.0)):
-    """3D-2D correspondences as Tracking::TrackWithPnP builds them (tracking.cpp:364-401:
-    cv::Point3f landmark positions, cv::Point2f current-frame feature positions): points seen by a
-    camera at a random T_cw, pixel noise, a fraction of wrong matches (random pixels).  Returns a
-    dict: obj (n x 3 float32), img (n x 2 float32), intr, pose (T_cw qx qy qz qw tx ty tz),
-    R, t, outlier (bool per correspondence)."""
-    rng = np.random.default_rng(seed)
+def _pnp_geometry(rng, n, outlier_frac, noise_px, width, height, intr, z_range):
+    """World points (float64) seen at pixels uv by a camera at a random T_cw = (q | R, t), pixel noise,
+    a fraction `outlier_frac` of the pixels replaced by random ones (flags in `out`)."""
     fx, fy, cx, cy = intr
     u = rng.uniform(0, width, n)
     v = rng.uniform(0, height, n)
@@ -392,10 +387,64 @@ def make_pnp_problem(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noi
     uv = np.stack([u, v], -1) + rng.normal(0, noise_px, (n, 2))
     out = rng.random(n) < outlier_frac
     uv[out] = np.stack([rng.uniform(0, width, out.sum()), rng.uniform(0, height, out.sum())], -1)
+    return pw, uv, out, q, R, t
+
+
+def make_pnp_problem(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noise_px: float = 0.5,
+                     width: int = 640, height: int = 480, intr=(FX, FY, CX, CY), z_range=(1.0, 6.0)):
+    """3D-2D correspondences as Tracking::TrackWithPnP builds them (tracking.cpp:364-401:
+    cv::Point3f landmark positions, cv::Point2f current-frame feature positions): points seen by a
+    camera at a random T_cw, pixel noise, a fraction of wrong matches (random pixels).  Returns a
+    dict: obj (n x 3 float32), img (n x 2 float32), intr, pose (T_cw qx qy qz qw tx ty tz),
+    R, t, outlier (bool per correspondence)."""
+    rng = np.random.default_rng(seed)
+    pw, uv, out, q, R, t = _pnp_geometry(rng, n, outlier_frac, noise_px, width, height, intr, z_range)
     if q[3] < 0:
         q = -q
     return {"obj": pw.astype(np.float32), "img": uv.astype(np.float32), "intr": np.array(intr, np.float64),
             "pose": np.concatenate([q, t]), "R": R, "t": t, "outlier": out}
+
+
+def make_track_scene(seed: int, n_feat: int = 300, *, wrong_frac: float = 0.3, noise_px: float = 0.5,
+                     max_flips: int = 24, kf_shift_px: float = 6.0, width: int = 640, height: int = 480,
+                     intr=(FX, FY, CX, CY), z_range=(1.0, 6.0)):
+    """What Tracking::TrackWithPnP (tracking.cpp:332-455) reads, on make_pnp_problem's geometry: a last
+    keyframe of n_feat features, each holding a landmark, and a current frame that sees the same
+    landmarks from the true pose T_cw, its keypoints stored in a permuted order.  A fraction
+    `wrong_frac` of the features is matched to a keypoint at a random pixel (a wrong match).
+
+    Descriptors (32 bytes): the current frame's are random; keyframe feature i's is its keypoint's with
+    flips[i] (0..max_flips) bits flipped, so the best Hamming distance of feature i is flips[i] and the
+    second best that of an unrelated random row (about 128 - 3 * 8 at the least): the ratio test passes
+    and Match(last_keyframe, curr) returns `matches` (query i, train train_of[i], distance flips[i]).
+
+    Returns a dict: kf_uv (n x 2 float64, the keyframe's own pixels: the current ones shifted by a
+    few px, so the parallax is known), lm_id (uint64), flags (uint8: has_landmark), lm_pos (n x 3
+    float64, not float-representable), curr_xy (n x 2 float32, permuted), train_of (int32: the keypoint
+    of feature i), desc_kf / desc_curr (n x 32 uint8), flips, matches (MATCH_DTYPE-compatible record
+    array), wrong (bool), intr, pose (T_cw qx qy qz qw tx ty tz), R, t."""
+    rng = np.random.default_rng(seed)
+    pw, uv, wrong, q, R, t = _pnp_geometry(rng, n_feat, wrong_frac, noise_px, width, height, intr, z_range)
+    if q[3] < 0:
+        q = -q
+    perm = rng.permutation(n_feat).astype(np.int32)
+    curr_xy = np.zeros((n_feat, 2), np.float32)
+    curr_xy[perm] = uv.astype(np.float32)
+    kf_uv = uv + rng.normal(0, kf_shift_px, (n_feat, 2))
+    desc_curr = rng.integers(0, 256, (n_feat, 32), dtype=np.uint8)
+    flips = rng.integers(0, max_flips + 1, n_feat).astype(np.int32)
+    bits = np.unpackbits(desc_curr[perm], axis=1)
+    for i in range(n_feat):
+        bits[i, rng.choice(256, flips[i], replace=False)] ^= 1
+    desc_kf = np.packbits(bits, axis=1)
+    matches = np.zeros(n_feat, [("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")])
+    matches["query_idx"] = np.arange(n_feat)
+    matches["train_idx"] = perm
+    matches["distance"] = flips
+    return {"kf_uv": kf_uv, "lm_id": (1000 + 7 * np.arange(n_feat)).astype(np.uint64),
+            "flags": np.ones(n_feat, np.uint8), "lm_pos": pw, "curr_xy": curr_xy, "train_of": perm,
+            "desc_kf": desc_kf, "desc_curr": desc_curr, "flips": flips, "matches": matches, "wrong": wrong,
+            "intr": np.array(intr, np.float64), "pose": np.concatenate([q, t]), "R": R, "t": t}
 
 
 def make_two_view(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noise_px: float = 0.5,
