@@ -650,6 +650,89 @@ int vx_track_pnp_host_async(vx_ctx* ctx, vx_dmap* map, uint64_t last_kf_id, cons
 /* threads of the pair-gather workgroup (its compaction chunk; for tests of the chunk boundaries) */
 int vx_track_block(void);
 
+/* ---------------------------------------------------------------- map culling on the resident map (cull.hip)
+ * <- Tracking::CullLandmarks (tracking.cpp:652-750), Tracking::CullKeyFrames (:775-840) and
+ *    Tracking::RemoveKeyFrame (:752-773), what Tracking::CreateKeyFrame runs before LocalBA
+ *    (:76-84): the decision (a reprojection of every observation of every landmark; a redundancy count
+ *    over every keyframe's features) and the edit of the map's device arrays run in kernels, the
+ *    culled lists come back with one synchronisation and the map's host mirrors follow them.  The map
+ *    afterwards is the map the same decisions leave through vx_dmap_set_landmark_bad /
+ *    vx_dmap_set_features / vx_dmap_remove_landmarks / vx_dmap_remove_observations /
+ *    vx_dmap_remove_keyframe. */
+typedef struct {                          /* Tracking::Options, "Map culling" (tracking.h:33-40) */
+    int32_t min_landmark_observations;    /* 2 */
+    int32_t min_landmarks_for_culling;    /* 200 */
+    int32_t min_keyframes_for_culling;    /* 3 */
+    int32_t max_keyframes;                /* 30 */
+    int32_t kf_min_shared_observations;   /* 3 */
+    int32_t reserved;
+    double kf_redundant_ratio;            /* 0.9 */
+    double landmark_max_reproj_error;     /* 5.0 */
+} vx_cull_options;
+void vx_cull_default_options(vx_cull_options* o);
+
+/* why a landmark left, in the order CullLandmarks tests (tracking.cpp:666-722) */
+#define VX_CULL_ALREADY_BAD 1       /* IsBad()                                         (:666) */
+#define VX_CULL_FEW_OBSERVATIONS 2  /* ObservationCount() < min_landmark_observations  (:670) */
+#define VX_CULL_NO_PROJECTION 3     /* no observation passed the checks of :681-701    (:713) */
+#define VX_CULL_LARGE_ERROR 4       /* an error > 2 * landmark_max_reproj_error        (:707) */
+#define VX_CULL_MEAN_ERROR 5        /* err_sum / cnt > landmark_max_reproj_error       (:719) */
+
+typedef struct {
+    uint64_t lm_id;
+    int32_t row;                /* the landmark's row in the map (insertion order) */
+    int32_t reason;             /* VX_CULL_* */
+    int32_t n_projected;        /* observations projected when the decision fell (insertion order; the walk
+                                   stops at the first large error, :709); 0 for ALREADY_BAD / FEW_OBSERVATIONS */
+    int32_t reserved;
+    double mean_err;            /* err_sum / cnt for MEAN_ERROR (summed in insertion order), else 0 */
+} vx_cull_landmark;
+typedef struct {                /* a feature reset to landmark_id_ = 0, has_landmark = false, is_outlier = true */
+    uint64_t kf_id;
+    int32_t kf_row;             /* the keyframe's row in the map */
+    int32_t feat_idx;
+} vx_cull_feature;
+
+/* <- Tracking::CullLandmarks (tracking.cpp:652-750).  Nothing happens below min_landmarks_for_culling
+ * live landmarks (:656).  Otherwise every live landmark is tested as :666-722 do (an observation's
+ * keyframe is looked up among the live keyframes; is_outlier is not consulted) and the culled ones are
+ * removed as :729-747 do: each observed feature whose landmark_id_ is the landmark's is reset (no
+ * has_landmark check there), then Map::RemoveLandmark.  *n_landmarks landmarks left, *n_features
+ * features were reset (either may be NULL); the lists: vx_dmap_cull_results.  Runs on ctx's stream (it
+ * waits for the map context's stream first when ctx is another context) and synchronises once. */
+int vx_dmap_cull_landmarks(vx_ctx* ctx, vx_dmap* map, const vx_cull_options* opt, int* n_landmarks, int* n_features);
+/* The counts of Tracking::CullKeyFrames' loop (tracking.cpp:804-820) for every live keyframe in
+ * ascending id: total[i] = its features with has_landmark, redundant[i] = those whose landmark is in
+ * the map, not bad and has ObservationCount() >= kf_min_shared_observations.  No edit.  *n = live
+ * keyframes; VX_ERR_CAPACITY (with *n set) when cap is smaller.  One synchronisation. */
+int vx_dmap_keyframe_redundancy(vx_ctx* ctx, vx_dmap* map, const vx_cull_options* opt, int cap, uint64_t* kf_id,
+                                int32_t* total, int32_t* redundant, int* n);
+/* <- Tracking::CullKeyFrames (tracking.cpp:775-840).  Nothing happens at or below
+ * min_keyframes_for_culling live keyframes (:781).  protect_ids: last_keyframe_, init_frame_ and the
+ * current frame (:797-802; ids not in the map are ignored).  The first keyframe in ascending id with
+ * ratio = double(redundant) / double(total) > kf_redundant_ratio && (exceeded || ratio > 0.95) (:826-827,
+ * compared on the host in that expression) is removed as Tracking::RemoveKeyFrame does (:752-773:
+ * RemoveObservation + reset for each of its has_landmark features whose landmark is in the map, the
+ * others left as they are, then Map::RemoveKeyFrame), and CullLandmarks runs once more (:838, under
+ * its own gate).  *removed 0 / 1, *removed_kf_id and *ratio of the removed keyframe, *n_landmarks /
+ * *n_features as vx_dmap_cull_landmarks (the keyframe's own reset features included); outputs may be
+ * NULL.  Two synchronisations when a keyframe is removed (the counts, then the lists), else one. */
+int vx_dmap_cull_keyframes(vx_ctx* ctx, vx_dmap* map, const vx_cull_options* opt, const uint64_t* protect_ids,
+                           int n_protect, int* removed, uint64_t* removed_kf_id, double* ratio, int* n_landmarks,
+                           int* n_features);
+/* The lists of the map's last vx_dmap_cull_landmarks / vx_dmap_cull_keyframes (host memory owned by
+ * the map, filled before that call's last synchronisation, valid until the next vx_dmap_* edit; may be
+ * read again, e.g. with larger arrays): *n_lm landmark records in ascending landmark row; *n_feat
+ * feature records, the culled landmarks' in (landmark row, observation insertion order), then the
+ * removed keyframe's own features in feature order.  Arrays may be NULL; VX_ERR_CAPACITY when an array
+ * is given and its count exceeds its cap (the counts are set either way). */
+int vx_dmap_cull_results(vx_dmap* map, int cap_lm, vx_cull_landmark* lm_records, int cap_feat,
+                         vx_cull_feature* feat_records, int* n_lm, int* n_feat);
+/* threads of a landmark-scan workgroup (for tests of its boundaries) and the keyframe count up to
+ * which the scan keeps its keyframe table in LDS (above it the table is read from global memory) */
+int vx_cull_block(void);
+int vx_cull_lds_keyframes(void);
+
 /* <- E = cv::findEssentialMat(pts_last, pts_curr, K, cv::RANSAC, 0.999, 1.0, mask);
  *    inliers = cv::recoverPose(E, pts_last, pts_curr, K, R, t, mask)
  *    in Tracking::EstimatePoseByEssential (tracking.cpp:503-547).

@@ -81,6 +81,17 @@ struct vx_dmap {
         vx::DevBuf pkey, skey, perm, k2, v2, scnt, pc, pptr, kcnt, oflag, orank, bidx, ekey, eval, ekey2, tmp;
         vx::PinnedBuf rb;
     } sba;
+    // map culling (cull.hip): buffers sized by capacity and reused call after call, the pinned block
+    // the kernels write the culled lists into, and the lists of the last call (vx_dmap_cull_results)
+    struct Cull {
+        vx::DevBuf kin, geo;               // live keyframes in ascending id: host-built rows | R, t, intrinsics
+        vx::DevBuf reason, cnt, mean, nreset, blk_cnt, blk_off;  // per landmark row / per scan workgroup
+        vx::DevBuf odead;                  // per CSR entry: removed by this call's RemoveKeyFrame
+        vx::DevBuf red;                    // per live keyframe {total, redundant}
+        vx::PinnedBuf up_host, host, red_host;
+        std::vector<vx_cull_landmark> lm;  // the last call's records
+        std::vector<vx_cull_feature> feat;
+    } cull;
     ~vx_dmap();
 };
 

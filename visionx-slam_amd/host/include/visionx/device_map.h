@@ -53,6 +53,10 @@ public:
     // every keyframe (id order) and landmark of an existing map, with their observations
     void Mirror(const Map& map);
 
+    // after a removal the resident map made itself (vx_dmap_cull_*, culling.h): the row tables follow
+    void DroppedLandmark(int64_t row, uint64_t lm_id);
+    void DroppedKeyFrame(uint64_t kf_id);
+
     // queued edits to the device (Optimize does this itself)
     void Flush();
     vx_dmap* handle() { return dm_; }

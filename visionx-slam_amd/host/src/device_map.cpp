@@ -119,6 +119,19 @@ void DeviceMap::RemoveLandmark(uint64_t lm_id) {
     }
 }
 
+void DeviceMap::DroppedLandmark(int64_t row, uint64_t lm_id) {
+    if (row >= 0 && row < (int64_t)landmarks_.size()) landmarks_[row] = nullptr;
+    auto it = lm_row_.find(lm_id);
+    if (it != lm_row_.end() && it->second == row) lm_row_.erase(it);
+}
+
+void DeviceMap::DroppedKeyFrame(uint64_t kf_id) {
+    auto it = kf_row_.find(kf_id);
+    if (it == kf_row_.end()) return;
+    frames_[it->second] = nullptr;
+    kf_row_.erase(it);
+}
+
 void DeviceMap::SetBad(uint64_t lm_id, bool bad) {
     Flush();
     const uint8_t b = bad ? 1 : 0;

@@ -97,6 +97,8 @@ EXPORTS = [
     "vx_match_batch_fetch", "vx_orb_extract_batch", "vx_match_knn2_ratio_batch", "vx_orb_set_order",
     "vx_orb_get_order", "vx_orb_set_debug", "vx_orb_debug_read", "vx_test_retain_best",
     "vx_track_default_options", "vx_orb_slot_keypoints", "vx_track_pnp_async", "vx_track_pnp_fetch", "vx_track_block", "vx_track_pnp_host_async",
+    "vx_cull_default_options", "vx_dmap_cull_landmarks", "vx_dmap_keyframe_redundancy", "vx_dmap_cull_keyframes",
+    "vx_dmap_cull_results", "vx_cull_block", "vx_cull_lds_keyframes",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -186,6 +188,16 @@ def lib():
         L.vx_track_pnp_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.vx_track_pnp_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_cull_default_options.restype = None
+        L.vx_cull_default_options.argtypes = [C.c_void_p]
+        L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.vx_dmap_keyframe_redundancy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(C.c_int)]
+        L.vx_dmap_cull_keyframes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.vx_dmap_cull_results.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int)]
         L.vx_ba_shard_of.restype = C.c_uint32
         L.vx_ba_shard_of.argtypes = [C.c_uint64, C.c_int]
         _lib = L
@@ -260,6 +272,39 @@ def track_options(min_matches=None, min_inliers=None, max_iterations=None, repro
         if v is not None:
             o["pnp"][k] = v
     return o
+
+
+# vx_cull_options / vx_cull_landmark / vx_cull_feature (include/vx_slam.h; sizes pinned in csrc/cull.hip)
+CULL_OPTIONS_DTYPE = np.dtype([("min_landmark_observations", "<i4"), ("min_landmarks_for_culling", "<i4"),
+                               ("min_keyframes_for_culling", "<i4"), ("max_keyframes", "<i4"),
+                               ("kf_min_shared_observations", "<i4"), ("reserved", "<i4"),
+                               ("kf_redundant_ratio", "<f8"), ("landmark_max_reproj_error", "<f8")])
+CULL_LANDMARK_DTYPE = np.dtype([("lm_id", "<u8"), ("row", "<i4"), ("reason", "<i4"), ("n_projected", "<i4"),
+                                ("reserved", "<i4"), ("mean_err", "<f8")])
+CULL_FEATURE_DTYPE = np.dtype([("kf_id", "<u8"), ("kf_row", "<i4"), ("feat_idx", "<i4")])
+CULL_ALREADY_BAD, CULL_FEW_OBSERVATIONS, CULL_NO_PROJECTION, CULL_LARGE_ERROR, CULL_MEAN_ERROR = range(1, 6)
+
+
+def cull_options(**fields):
+    """Tracking::Options' map-culling fields (tracking.h:33-40) with the reference's defaults, any of
+    them overridable by name."""
+    o = np.zeros((), CULL_OPTIONS_DTYPE)
+    lib().vx_cull_default_options(_p(o))
+    for k, v in fields.items():
+        if k not in CULL_OPTIONS_DTYPE.names or k == "reserved":
+            raise TypeError(f"cull_options: unknown field {k!r}")
+        o[k] = v
+    return o
+
+
+def cull_block() -> int:
+    """landmark rows of one scan workgroup (the unit of the culled lists' ordered compaction)"""
+    return int(lib().vx_cull_block())
+
+
+def cull_lds_keyframes() -> int:
+    """live keyframes up to which the landmark scan holds its keyframe table in LDS"""
+    return int(lib().vx_cull_lds_keyframes())
 
 
 def track_block() -> int:
@@ -1073,6 +1118,57 @@ class DMap:
         l_rows = np.ctypeslib.as_array(lr, (m,)).astype(np.int64)
         l_pos = np.ctypeslib.as_array(lp, (m, 4))[:, :3].copy()
         return k_rows, k_pose, l_rows, l_pos
+
+    def cull_results(self):
+        """vx_dmap_cull_results: the last cull call's (landmark records, feature records)."""
+        nl, nf = C.c_int(0), C.c_int(0)
+        self.ctx._check(lib().vx_dmap_cull_results(self._h, 0, None, 0, None, C.byref(nl), C.byref(nf)))
+        lm = np.zeros(max(nl.value, 1), CULL_LANDMARK_DTYPE)
+        ft = np.zeros(max(nf.value, 1), CULL_FEATURE_DTYPE)
+        self.ctx._check(lib().vx_dmap_cull_results(self._h, len(lm), _p(lm), len(ft), _p(ft), C.byref(nl),
+                                                   C.byref(nf)))
+        return lm[:nl.value], ft[:nf.value]
+
+    def cull_landmarks(self, opts=None, ctx=None):
+        """vx_dmap_cull_landmarks: Tracking::CullLandmarks on the resident map (decision and edit on the
+        device, one synchronisation).  Returns {"landmarks": CULL_LANDMARK_DTYPE records in ascending
+        row, "features": CULL_FEATURE_DTYPE records of the features reset}.  `ctx`: another context
+        of the same device to run on."""
+        o = cull_options() if opts is None else opts
+        c = self.ctx if ctx is None else ctx
+        nl, nf = C.c_int(0), C.c_int(0)
+        c._check(lib().vx_dmap_cull_landmarks(c.handle, self._h, _p(o), C.byref(nl), C.byref(nf)))
+        lm, ft = self.cull_results()
+        assert len(lm) == nl.value and len(ft) == nf.value
+        return {"landmarks": lm, "features": ft}
+
+    def keyframe_redundancy(self, opts=None, ctx=None):
+        """vx_dmap_keyframe_redundancy: {"kf_id", "total", "redundant"} of every live keyframe in
+        ascending id (the counts of Tracking::CullKeyFrames' loop); no edit."""
+        o = cull_options() if opts is None else opts
+        c = self.ctx if ctx is None else ctx
+        cap = max(self.live_counts()["kf"], 1)
+        ids, tot, red = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int(0)
+        c._check(lib().vx_dmap_keyframe_redundancy(c.handle, self._h, _p(o), cap, _p(ids), _p(tot), _p(red),
+                                                   C.byref(n)))
+        return {"kf_id": ids[:n.value], "total": tot[:n.value], "redundant": red[:n.value]}
+
+    def cull_keyframes(self, opts=None, protect=(), ctx=None):
+        """vx_dmap_cull_keyframes: Tracking::CullKeyFrames (with RemoveKeyFrame and the trailing
+        CullLandmarks) on the resident map.  `protect`: the ids of last_keyframe_, init_frame_ and the
+        current frame.  Returns {"removed": bool, "kf_id", "ratio", "landmarks", "features"}."""
+        o = cull_options() if opts is None else opts
+        c = self.ctx if ctx is None else ctx
+        pr = np.ascontiguousarray(list(protect), np.uint64)
+        rem, nl, nf = C.c_int(0), C.c_int(0), C.c_int(0)
+        kid, ratio = C.c_uint64(0), C.c_double(0.0)
+        c._check(lib().vx_dmap_cull_keyframes(c.handle, self._h, _p(o), _p(pr) if len(pr) else None, len(pr),
+                                              C.byref(rem), C.byref(kid), C.byref(ratio), C.byref(nl), C.byref(nf)))
+        lm, ft = self.cull_results()
+        assert len(lm) == nl.value and len(ft) == nf.value
+        return {"removed": bool(rem.value), "kf_id": int(kid.value), "ratio": float(ratio.value), "landmarks": lm,
+                "features": ft}
 
     def close(self):
         if self._h:

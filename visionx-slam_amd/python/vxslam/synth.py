@@ -479,3 +479,215 @@ def make_two_view(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noise_
     b[out] = np.stack([rng.uniform(0, width, out.sum()), rng.uniform(0, height, out.sum())], -1)
     return {"pts_last": a.astype(np.float32), "pts_curr": b.astype(np.float32), "intr": np.array(intr, np.float64),
             "R": R, "t": t, "t_dir": t / np.linalg.norm(t), "outlier": out}
+
+
+# --------------------------------------------------------------------------- map culling
+def _project_rows(m, lm_rows, kf_rows):
+    """camera-frame points and pixels of landmark rows seen from keyframe rows (R from the quaternion
+    as Eigen's toRotationMatrix, pc = R p + t, common/projection.h:16-25)"""
+    pose = m["kf_pose"].reshape(-1, 7)[kf_rows]
+    R = quat_to_mat(pose[:, :4])
+    pc = np.einsum("oij,oj->oi", R, m["lm_pos"].reshape(-1, 3)[lm_rows]) + pose[:, 4:]
+    intr = m["kf_intr"].reshape(-1, 4)[kf_rows]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uv = np.stack([intr[:, 0] * (pc[:, 0] / pc[:, 2]) + intr[:, 2], intr[:, 1] * (pc[:, 1] / pc[:, 2]) + intr[:, 3]], -1)
+    return pc, uv
+
+
+def cull_state(m):
+    """The membership state Tracking's culling changes, added to a BAMap in place when absent:
+    kf_alive (0 after Map::RemoveKeyFrame; a later row may hold the id again), lm_removed (1 after
+    Map::RemoveLandmark), obs_live (0 after Landmark::RemoveObservation).  Rows are storage rows."""
+    m.setdefault("kf_alive", np.ones(len(m["kf_id"]), np.uint8))
+    m.setdefault("lm_removed", np.zeros(len(m["lm_id"]), np.uint8))
+    m.setdefault("obs_live", np.ones(len(m["obs_kf_id"]), np.uint8))
+    return m
+
+
+def cull_margins(m, tau=5.0):
+    """How far the map is from each threshold Tracking::CullLandmarks compares against
+    (tracking.cpp:652-750), as relative distances over every observation the walk can project:
+    {"err": min |err - 2 tau| / 2 tau, "mean": min |mean - tau| / tau over the landmarks without a
+    large error, "z": min |pc.z - 1e-6| / 1e-6}.  A decision made in another rounding order is the same
+    decision while these stay far above that order's error."""
+    cull_state(m)
+    optr = m["lm_obs_ptr"]
+    lm = np.repeat(np.arange(len(m["lm_id"])), np.diff(optr))
+    alive = np.nonzero(m["kf_alive"])[0]
+    row_of = {int(m["kf_id"][k]): int(k) for k in alive}
+    kf = np.array([row_of.get(int(i), -1) for i in m["obs_kf_id"]], np.int64)
+    fi = m["obs_feat_idx"].astype(np.int64)
+    nf = np.diff(m["kf_feat_ptr"])
+    ok = (m["obs_live"] > 0) & (m["lm_removed"][lm] == 0) & (m["lm_bad"][lm] == 0) & (kf >= 0)
+    ok &= (fi >= 0) & (fi < nf[np.maximum(kf, 0)])
+    g = m["kf_feat_ptr"][np.maximum(kf, 0)] + np.where(ok, fi, 0)
+    ok &= ((m["feat_flags"][g] & 1) > 0) & (m["feat_lm_id"][g] == m["lm_id"][lm]) & (m["kf_has_cam"][np.maximum(kf, 0)] > 0)
+    sel = np.nonzero(ok)[0]
+    out = {"err": np.inf, "mean": np.inf, "z": np.inf}
+    if not len(sel):
+        return out
+    pc, uv = _project_rows(m, lm[sel], kf[sel])
+    out["z"] = float((np.abs(pc[:, 2] - 1e-6) / 1e-6).min())
+    front = pc[:, 2] > 1e-6
+    err = np.hypot(*(m["feat_uv"].reshape(-1, 2)[g[sel][front]] - uv[front]).T)
+    if len(err):
+        out["err"] = float((np.abs(err - 2 * tau) / (2 * tau)).min())
+        rows = lm[sel][front]
+        s = np.bincount(rows, err, len(m["lm_id"]))
+        c = np.bincount(rows, minlength=len(m["lm_id"]))
+        large = np.bincount(rows, err > 2 * tau, len(m["lm_id"])) > 0
+        use = (c > 0) & ~large
+        if use.any():
+            out["mean"] = float((np.abs(s[use] / c[use] - tau) / tau).min())
+    return out
+
+
+def make_cull_scene(seed: int, n_kf: int = 10, n_lm: int = 2000, *, special: bool = True, tau: float = 5.0,
+                    min_margin: float = 1e-9, **ba_kw) -> BAMap:
+    """A map for Tracking::CullLandmarks / CullKeyFrames (tracking.cpp:652-840): make_ba_map (bad
+    landmarks, single-observation landmarks, features naming ids that are not in the map; the larger
+    `lm_sigma`, the more reprojection culls) with the membership state of cull_state, plus — with
+    `special` — hand-placed keyframes and landmarks that each reach one branch of the walk:
+
+      keyframes   S0, S1 (ordinary), D (removed from the map), Y (id removed and inserted again: a dead
+                  row and a live one), C (no camera), B (looks away: points lie behind it), Z (no
+                  feature holds a landmark), W0..W69 (one feature each)
+      landmarks   (name -> row in m["special"]) dead_kf: one observation names D (still counts towards
+                  ObservationCount); reinserted / reinserted_bad: observed through Y's live row (small /
+                  large error there, garbage in the dead row); oor / oor_cull: a feature index past the
+                  keyframe's features; other / other_cull: the feature points at another landmark;
+                  nohas_keep / nohas_cull: the feature carries the id without has_landmark (skipped by
+                  the walk, reset by the removal); behind: pc.z < 0 in B; nocam: observed by C;
+                  wave_cull / wave_keep: 70 observations (W0..W69), the only large error the last /
+                  none; all_skipped / all_skipped_reset: every observation skipped (NO_PROJECTION; the
+                  second one's features are still reset); mean: errors 4 and 8; removed: a removed
+                  landmark that features of S0 and S1 still name.
+
+    Asserts cull_margins(m, tau) > min_margin on all three."""
+    m = cull_state(make_ba_map(seed, n_kf, n_lm, **ba_kw))
+    if special:
+        _add_cull_specials(m, np.random.default_rng(seed ^ 0xC0117))
+    mg = cull_margins(m, tau)
+    assert min(mg.values()) > min_margin, mg
+    m["margins"] = mg
+    return m
+
+
+def _add_cull_specials(m, rng):
+    base_pose = m["kf_pose"].reshape(-1, 7)
+    nb = len(base_pose)
+    intr = m["kf_intr"].reshape(-1, 4)[0]
+    kfs, lms = [], []  # [id, pose, has_cam, alive, feats [(uv, lm_id, flags)]], [id, pos, bad, removed, obs [(kf_id, fi)]]
+
+    def new_kf(kid, pose, cam=1, alive=1):
+        kfs.append([kid, np.array(pose, np.float64), cam, alive, []])
+        return len(kfs) - 1
+
+    def feat(k, uv, lm_id, flags=1):
+        kfs[k][4].append((np.array(uv, np.float64), int(lm_id), flags))
+        return len(kfs[k][4]) - 1
+
+    def proj(k, p):
+        q, t = kfs[k][1][:4], kfs[k][1][4:]
+        pc = quat_to_mat(q) @ p + t
+        return np.array([intr[0] * (pc[0] / pc[2]) + intr[2], intr[1] * (pc[1] / pc[2]) + intr[3]])
+
+    ids = iter(range(9_000_001, 9_100_000))
+    names = {}
+
+    def new_lm(name, bad=0, removed=0):
+        p = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.2, 0.2), rng.uniform(2.5, 4.0)])
+        lms.append([next(ids), p, bad, removed, []])
+        names[name] = len(lms) - 1
+        return len(lms) - 1
+
+    def see(l, k, err=1.0, flags=1, lm_id=None, uv=None):
+        """landmark l observed by keyframe k through a new feature `err` px (a 3-4-5 offset) off its projection"""
+        if uv is None:
+            uv = proj(k, lms[l][1]) + np.array([0.6, 0.8]) * err
+        fi = feat(k, uv, lms[l][0] if lm_id is None else lm_id, flags)
+        lms[l][4].append((kfs[k][0], fi))
+        return fi
+
+    S0 = new_kf(1000, base_pose[0])
+    S1 = new_kf(1001, base_pose[min(1, nb - 1)])
+    D = new_kf(1002, base_pose[0], alive=0)
+    Y1 = new_kf(1003, base_pose[0], alive=0)
+    C = new_kf(1004, base_pose[0], cam=0)
+    flip = quat_mul(np.array([0.0, 1.0, 0.0, 0.0]), base_pose[0][:4])  # half a turn about y
+    B = new_kf(1005, np.concatenate([flip, quat_to_mat(np.array([0.0, 1.0, 0.0, 0.0])) @ base_pose[0][4:]]))
+    Z = new_kf(1006, base_pose[0])
+    W = [new_kf(2000 + i, base_pose[i % nb]) for i in range(70)]
+    Y2 = new_kf(1003, base_pose[min(1, nb - 1)])  # the id again: a later row
+    for _ in range(3):
+        feat(Z, rng.uniform(0, 400, 2), 0, 0)
+        feat(Y1, rng.uniform(0, 400, 2), 0, 0)  # so that Y2's feature indices differ from Y1's... (Y1 holds more)
+
+    l = new_lm("dead_kf")
+    see(l, S0), see(l, D)
+    for name, e in (("reinserted", 1.0), ("reinserted_bad", 30.0)):
+        l = new_lm(name)
+        see(l, S0)
+        fi = see(l, Y2, err=e)
+        while len(kfs[Y1][4]) <= fi:  # the dead row holds a feature at that index too, far off
+            feat(Y1, [5000.0, 5000.0], lms[l][0], 1)
+        kfs[Y1][4][fi] = (np.array([5000.0, 5000.0]), lms[l][0], 1)
+    for name, e in (("oor", 1.0), ("oor_cull", 30.0)):
+        l = new_lm(name)
+        see(l, S0, err=e)
+        lms[l][4].append((kfs[S1][0], 100_000))
+    for name, e in (("other", 1.0), ("other_cull", 30.0)):
+        l = new_lm(name)
+        see(l, S0, err=e)
+        see(l, S1, err=30.0 if e == 1.0 else 1.0, lm_id=lms[names["oor"]][0])
+    l = new_lm("nohas_keep")
+    see(l, S0), see(l, S1, err=30.0, flags=0)
+    l = new_lm("nohas_cull")
+    see(l, S0, err=30.0), see(l, S1, flags=0)
+    l = new_lm("behind")
+    see(l, S0), see(l, B, uv=[100.0, 100.0])
+    l = new_lm("nocam")
+    see(l, S0), see(l, C, uv=[100.0, 100.0])
+    l = new_lm("wave_cull")
+    for i, k in enumerate(W):
+        see(l, k, err=30.0 if i == 69 else 0.5 + 0.01 * i)
+    l = new_lm("wave_keep")
+    for i, k in enumerate(W):
+        see(l, k, err=0.5 + 0.01 * i)
+    l = new_lm("all_skipped")
+    see(l, D), lms[l][4].append((kfs[S1][0], 100_001))
+    l = new_lm("all_skipped_reset")
+    see(l, C, uv=[50.0, 60.0]), see(l, S1, flags=0)
+    l = new_lm("mean")
+    see(l, S0, err=4.0), see(l, S1, err=8.0)
+    l = new_lm("removed", removed=1)
+    see(l, S0), see(l, S1)
+    assert len(kfs[Y1][4]) != len(kfs[Y2][4])
+
+    # ---- append to the map's arrays (storage rows: keyframes then landmarks, in creation order)
+    k0 = len(m["kf_id"])
+    m["kf_id"] = np.concatenate([m["kf_id"], np.array([k[0] for k in kfs], np.uint64)])
+    m["kf_pose"] = np.concatenate([m["kf_pose"].reshape(-1, 7), np.stack([k[1] for k in kfs])])
+    m["kf_intr"] = np.concatenate([m["kf_intr"].reshape(-1, 4), np.tile(intr, (len(kfs), 1))])
+    m["kf_has_cam"] = np.concatenate([m["kf_has_cam"], np.array([k[2] for k in kfs], np.uint8)])
+    m["kf_alive"] = np.concatenate([m["kf_alive"], np.array([k[3] for k in kfs], np.uint8)])
+    cnt = np.array([len(k[4]) for k in kfs], np.int64)
+    m["kf_feat_ptr"] = np.concatenate([m["kf_feat_ptr"], m["kf_feat_ptr"][-1] + np.cumsum(cnt)]).astype(np.int64)
+    fl = [f for k in kfs for f in k[4]]
+    m["feat_uv"] = np.concatenate([m["feat_uv"].reshape(-1, 2), np.stack([f[0] for f in fl])])
+    m["feat_lm_id"] = np.concatenate([m["feat_lm_id"], np.array([f[1] for f in fl], np.uint64)])
+    m["feat_flags"] = np.concatenate([m["feat_flags"], np.array([f[2] for f in fl], np.uint8)])
+    l0 = len(m["lm_id"])
+    m["lm_id"] = np.concatenate([m["lm_id"], np.array([x[0] for x in lms], np.uint64)])
+    m["lm_pos"] = np.concatenate([m["lm_pos"].reshape(-1, 3), np.stack([x[1] for x in lms])])
+    m["lm_bad"] = np.concatenate([m["lm_bad"], np.array([x[2] for x in lms], np.uint8)])
+    m["lm_removed"] = np.concatenate([m["lm_removed"], np.array([x[3] for x in lms], np.uint8)])
+    ocnt = np.array([len(x[4]) for x in lms], np.int64)
+    m["lm_obs_ptr"] = np.concatenate([m["lm_obs_ptr"], m["lm_obs_ptr"][-1] + np.cumsum(ocnt)]).astype(np.int64)
+    ol = [o for x in lms for o in x[4]]
+    m["obs_kf_id"] = np.concatenate([m["obs_kf_id"], np.array([o[0] for o in ol], np.uint64)])
+    m["obs_feat_idx"] = np.concatenate([m["obs_feat_idx"], np.array([o[1] for o in ol], np.uint64)])
+    m["obs_live"] = np.concatenate([m["obs_live"], np.ones(len(ol), np.uint8)])
+    m["special"] = {n: l0 + r for n, r in names.items()}
+    m["special_kf"] = {"S0": k0 + S0, "S1": k0 + S1, "D": k0 + D, "Y_dead": k0 + Y1, "Y": k0 + Y2, "C": k0 + C,
+                       "B": k0 + B, "Z": k0 + Z, "W": [k0 + w for w in W]}
