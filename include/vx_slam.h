@@ -32,6 +32,9 @@
  *                            Tracking::EstimatePoseByEssential   core/frontend/tracking.cpp:503-547
  *   vx_dmap_*             <- visionx::Map (map.h:13-35) kept resident on the device, updated like
  *                            Map::InsertKeyFrame / InsertLandmark / Landmark::AddObservation
+ *   vx_dmap_create_keyframe* <- Tracking::CreateKeyFrame's insertion: CreateLandmarksFromDepth,
+ *                            TriangulateWithLastKeyFrame, Map::InsertKeyFrame on the resident map
+ *                                                                core/frontend/tracking.cpp:577-584
  *   vx_ba_plan_create_dmap <- the gather of local_ba.cpp:42-108 from the resident map
  *   vx_sba_*              (no reference counterpart: north_star's Schur-complement dense solve)
  *
@@ -733,6 +736,92 @@ int vx_dmap_cull_results(vx_dmap* map, int cap_lm, vx_cull_landmark* lm_records,
 int vx_cull_block(void);
 int vx_cull_lds_keyframes(void);
 
+/* ---------------------------------------------------------------- keyframe creation on the resident map (keyframe.hip)
+ * <- Tracking::CreateKeyFrame (tracking.cpp:577-584): CreateLandmarksFromDepth(curr) (:586-650), then
+ *    TriangulateWithLastKeyFrame(last, curr) (:856-945, whose has_landmark test on the current side sees
+ *    the depth landmarks just made), then Map::InsertKeyFrame (:581) — as one stream-ordered sequence
+ *    over the resident map with one synchronisation.  The last keyframe's feature positions, flags,
+ *    pose and intrinsics are read from the map's rows (after a LocalBA its pose is current only
+ *    there), never passed in.  After a successful call the map is the map this sequence leaves:
+ *      vx_dmap_add_landmarks     ids first_landmark_id + rank in creation order, bad = 0
+ *      vx_dmap_add_observations  creation order: a depth landmark adds (kf_id, i); a triangulated one
+ *                                (last_kf_id, queryIdx) then (kf_id, trainIdx) (:916-917)
+ *      vx_dmap_set_features      last_kf_id's triangulated query features: id, has_landmark, not outlier
+ *      vx_dmap_add_keyframe      kf_id with the final links (unlinked features: id 0, flags 0)
+ *    device rows and host mirrors alike.  Creation order: the depth landmarks in feature order, then
+ *    the triangulated ones in match order (the first passing match per train feature wins). */
+typedef struct {
+    double tri_min_angle_deg;      /* 1.0  triangulation_min_angle_deg (tracking.h:43) */
+    double tri_max_reproj_error;   /* 5.0  triangulation_max_reproj_error (tracking.h:44) */
+} vx_keyframe_options;
+void vx_keyframe_default_options(vx_keyframe_options* o);
+
+/* error_bits of vx_keyframe_result: why a call returned VX_ERR_INVALID and left the map as it was */
+#define VX_KF_ERR_MATCH_RANGE 1   /* a match index outside either feature set (found on the device) */
+#define VX_KF_ERR_DUP_QUERY 2     /* a repeated query index (found on the device) */
+#define VX_KF_ERR_KF_LIVE 4       /* kf_id is already a live keyframe */
+#define VX_KF_ERR_NO_LAST 8       /* last_kf_id is not a live keyframe */
+#define VX_KF_ERR_NO_CAMERA 16    /* intr4 == NULL, or the last keyframe was inserted without a camera */
+#define VX_KF_ERR_ID_RANGE 32     /* an id of [first_landmark_id, first_landmark_id + cap_feat) is in the map */
+
+typedef struct {
+    int32_t n_feat;                /* features of the new keyframe (the device-side count, clamped to cap_feat) */
+    int32_t n_depth;               /* landmarks CreateLandmarksFromDepth made */
+    int32_t n_triangulated;        /* landmarks TriangulateWithLastKeyFrame made */
+    int32_t n_matches;             /* matches read (clamped to cap_matches; 0 without a last keyframe) */
+    uint64_t first_landmark_id;
+    uint64_t next_landmark_id;     /* first_landmark_id + n_depth + n_triangulated: the caller's landmark_id_ */
+    int32_t error_bits;            /* VX_KF_ERR_* */
+    int32_t reserved;
+} vx_keyframe_result;
+
+typedef struct {                   /* one created landmark */
+    uint64_t lm_id;
+    int32_t row;                   /* its row in the map */
+    int32_t kind;                  /* 0 depth, 1 triangulated */
+    int32_t feat_curr;             /* feature of the new keyframe */
+    int32_t feat_last;             /* feature of the last keyframe (-1 for depth) */
+    double pw[3];
+} vx_keyframe_landmark;
+
+/* The device-input form.  kf_id / pose7 (x y z w | t, T_cw) / intr4: the new keyframe.  Feature
+ * positions: row i = two floats at d_xy + i * stride_bytes (20 for the vx_keypoint rows of an extraction
+ * slot, vx_orb_slot_keypoints; 8 for packed float2), *d_n_feat rows (at most cap_feat), widened to
+ * double exactly as Feature::position is made from cv::KeyPoint::pt.  has_last == 0 skips the
+ * triangulation (the first frame of InitWithSecondFrame).  The match list Match(last, curr) (query =
+ * last keyframe feature, train = new feature): d_matches == NULL = the result of ctx's last
+ * vx_match_*_async (VX_ERR_STATE if none), else *d_n_matches rows (at most cap_matches).  d_depth:
+ * device image of `rows` rows of `cols` VX_DEPTH_* elements, row_stride bytes apart; NULL =
+ * Depth().empty().  Before enqueueing, every array of the map is grown for the worst case (cap_feat
+ * features and landmarks, 2 cap_feat observations); after that no count comes from the host.  Runs on
+ * ctx's stream (which first waits for the map context's stream when ctx is another context) and
+ * synchronises once.  VX_ERR_INVALID with result->error_bits set leaves the map exactly as it was
+ * (rows beyond the map's counts are scratch). */
+int vx_dmap_create_keyframe(vx_ctx* ctx, vx_dmap* map, uint64_t kf_id, const double* pose7, const double* intr4,
+                            const float* d_xy, int64_t stride_bytes, const int32_t* d_n_feat, int cap_feat,
+                            int has_last, uint64_t last_kf_id, const vx_match* d_matches,
+                            const int32_t* d_n_matches, int cap_matches, const void* d_depth, int depth_type,
+                            int rows, int cols, int64_t row_stride, uint64_t first_landmark_id,
+                            const vx_keyframe_options* opt, vx_keyframe_result* result);
+/* The host-input form (what visionx::KeyFrameLandmarks::CreateKeyFrame calls): feat_uv = n_feat rows
+ * of two doubles (Feature::position), a host match list and a host depth image (NULL = empty), staged
+ * into one pinned block and uploaded in one copy; then the same sequence. */
+int vx_dmap_create_keyframe_host(vx_ctx* ctx, vx_dmap* map, uint64_t kf_id, const double* pose7, const double* intr4,
+                                 const double* feat_uv, int n_feat, int has_last, uint64_t last_kf_id,
+                                 const vx_match* matches, int n_matches, const void* depth, int depth_type,
+                                 int rows, int cols, int64_t row_stride, uint64_t first_landmark_id,
+                                 const vx_keyframe_options* opt, vx_keyframe_result* result);
+/* The records of the map's last vx_dmap_create_keyframe*, one per created landmark in creation order
+ * (host memory owned by the map; empty after a rejected call).  `records` may be NULL;
+ * VX_ERR_CAPACITY (with *n set) when it is given and *n > cap. */
+int vx_dmap_create_results(vx_dmap* map, int cap, vx_keyframe_landmark* records, int* n);
+/* A live keyframe's feature rows read back from the device: uv (2 doubles), lm_id, flags per feature;
+ * any array may be NULL.  *n = its feature count; VX_ERR_CAPACITY when an array is given and *n > cap. */
+int vx_dmap_keyframe_features(vx_dmap* map, uint64_t kf_id, int cap, double* uv, uint64_t* lm_id, uint8_t* flags,
+                              int* n);
+/* threads of the commit workgroup (the chunk of its two ordered compactions; for tests of the boundaries) */
+int vx_keyframe_block(void);
+
 /* <- E = cv::findEssentialMat(pts_last, pts_curr, K, cv::RANSAC, 0.999, 1.0, mask);
  *    inliers = cv::recoverPose(E, pts_last, pts_curr, K, R, t, mask)
  *    in Tracking::EstimatePoseByEssential (tracking.cpp:503-547).
@@ -808,6 +897,8 @@ int vx_comm_info(vx_ctx* ctx, int* nranks, int* rank);
  * stage_mask: 0 = off, -1 = every stage, otherwise bit s enables stage s only (so a timed run
  * can bracket just the kernel it reports without perturbing the others). */
 int vx_prof_enable(vx_ctx* ctx, int stage_mask);
+/* the same with a 64-bit mask (stages 32 and up; vx_prof_enable's int sign-extends, so its -1 is still all) */
+int vx_prof_enable64(vx_ctx* ctx, uint64_t stage_mask);
 int vx_prof_count(void);
 const char* vx_prof_name(int stage);
 int vx_prof_read(vx_ctx* ctx, double* ms, int64_t* launches, int reset);

@@ -92,6 +92,22 @@ struct vx_dmap {
         std::vector<vx_cull_landmark> lm;  // the last call's records
         std::vector<vx_cull_feature> feat;
     } cull;
+    // keyframe creation (keyframe.hip): per-feature / per-match flags and points, sized by the call's
+    // capacities and reused call after call; the pinned block its commit kernel writes the header and
+    // the records into; the host-input form's staging; the records of the last call
+    // (vx_dmap_create_results)
+    struct Create {
+        vx::DevBuf dvalid, dpw, tvalid, tpw;  // depth per feature / triangulation per match
+        vx::DevBuf aux;                       // winner per feature | qseen per last-keyframe feature | error word
+        vx::PinnedBuf host;
+        vx::PinnedBuf in_host;                // vx_dmap_create_keyframe_host: one staged block ...
+        vx::DevBuf in;                        // ... uploaded in one copy
+        hipEvent_t in_event = nullptr;        // (recorded after that upload: the staging is reused once it has passed)
+        std::vector<vx_keyframe_landmark> rec;
+        ~Create() {
+            if (in_event) (void)hipEventDestroy(in_event);
+        }
+    } create;
     ~vx_dmap();
 };
 

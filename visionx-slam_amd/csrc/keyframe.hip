@@ -1,0 +1,665 @@
+// keyframe.hip — Tracking::CreateKeyFrame (core/frontend/tracking.cpp:577-584) on the device-resident
+// map: vx_dmap_create_keyframe / vx_dmap_create_keyframe_host.
+//
+// The reference runs CreateLandmarksFromDepth(curr) (:586-650), TriangulateWithLastKeyFrame(last,
+// curr) (:856-945) and Map::InsertKeyFrame(curr) (:581) one after the other, each loop marking
+// features as it goes.  Everything those loops read is resident — the new frame's keypoints (an
+// extraction slot), the match list (match.hip), the last keyframe's features, pose and intrinsics
+// (vx_dmap rows) — and everything they change is a row of the map, so the sequence is
+//
+//   k_kf_feat (per feature)  ->  k_kf_match (per match)  ->  k_kf_commit (1 workgroup)
+//
+// with no host step between and one synchronisation after it.
+//
+//   k_kf_feat    widens feature i's position to double, stores it (with an empty link) at the map's
+//                feature end, and evaluates the depth branch: flag + point per feature.
+//   k_kf_match   match k: index bounds and the repeated-query test into the error word; the
+//                has_landmark tests (the last keyframe's feat_fl row; the depth flag of the train
+//                feature, i.e. the sequential outcome of the depth loop having run first); the
+//                triangulation gate of lm_math.hpp with the last keyframe's pose and intrinsics read
+//                from their map rows; a passing match enters atomicMin(winner[train], k).
+//   k_kf_commit  validate-then-commit: reads the error word first and, when it is set, writes the
+//                header and nothing else.  Otherwise two ORDERED compactions — the features with a
+//                depth point, then the matches that passed and won their train feature — give every
+//                created landmark its rank: per chunk of kBlock items a wave64 ballot + mbcnt ranks
+//                inside the wave, the wave totals are summed in LDS, a running base carries over.
+//                No atomic decides a position, so ids, rows and observation order are the sequential
+//                loop's.  Rank r writes landmark row n_lm + r, its observation rows (one for depth,
+//                two for a triangulated landmark: last keyframe first, :916-917), their ids and
+//                id_row entries, the feature links of both keyframes and its record; thread 0 writes
+//                the keyframe's pose / intrinsics rows and the header.  Records and header go to a
+//                host-pinned block with plain stores: the end of the kernel releases them and the
+//                one stream synchronisation makes them the host's.
+//
+// The commit is ONE workgroup for the reason k_track_pairs is: both compactions are ordered over at
+// most a few thousand items, and a second workgroup would need a second launch or a grid barrier to
+// see the first one's totals.  LDS: 16 wave counts.
+//
+// Every row the kernels write lies beyond the map's used counts (scratch until the host mirrors
+// advance them) except the last keyframe's feature links and nothing at all on a rejected call, so a
+// rejected call leaves the map as it was.  The arrays are grown for the worst case before the
+// launches (cap_feat landmarks, 2 cap_feat observations: a feature is linked at most once), so the
+// device sequence needs no count from the host.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "vx_internal.hpp"
+#include "dmap.hpp"
+#include "lm_math.hpp"
+
+namespace vx {
+namespace {
+
+using namespace vx::lm;
+
+constexpr int kThreads = 256;
+constexpr int kBlock = 1024;
+constexpr int kWaves = kBlock / 64;
+
+struct KfArgs {
+    // the new keyframe
+    uint64_t kf_id, last_kf_id, first_id;
+    const uint8_t* xy;       // position rows: two floats (or doubles, xy_f64) at xy + i * stride
+    int64_t stride;
+    int xy_f64;
+    const int* n_feat;
+    int cap_feat;
+    int has_depth;
+    DepthView dv;            // depth image + the new keyframe's intrinsics and T_cw
+    // the last keyframe (rows of the map)
+    int has_last, k_last, nf_last;
+    int64_t f0_last;
+    const vx_match* m;
+    const int* n_matches;
+    int cap_matches;
+    double min_angle_rad, max_err;
+    // the map: arrays and the used counts the new rows follow
+    double *kf_pose, *kf_intr, *feat_uv;
+    uint64_t* feat_lm;
+    uint8_t* feat_fl;
+    uint64_t* lm_id;
+    double* lm_pos;
+    uint8_t* lm_bad;
+    int* obs_lm;
+    uint64_t *obs_kf, *obs_fi;
+    int64_t *obs_id, *id_row;
+    int k_new;
+    int64_t f0, n_lm0, n_obs0, n_ids0;
+    double pose[7], intr[4];
+    // scratch
+    int* dvalid;             // per feature: CreateLandmarksFromDepth made a landmark
+    double* dpw;
+    int* tvalid;             // per match: passed the triangulation gate
+    double* tpw;
+    int *winner, *qseen, *err;
+    // host-pinned outputs
+    vx_keyframe_result* hdr;
+    vx_keyframe_landmark* rec;
+};
+
+__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
+
+__global__ __launch_bounds__(kThreads) void k_kf_feat(KfArgs a) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const int n = clampi(*a.n_feat, a.cap_feat);
+    if (i >= n) return;
+    const uint8_t* p = a.xy + (int64_t)i * a.stride;
+    double x, y;
+    if (a.xy_f64) {
+        x = reinterpret_cast<const double*>(p)[0];
+        y = reinterpret_cast<const double*>(p)[1];
+    } else {  // Feature::position from cv::KeyPoint::pt: float -> double, exact
+        x = (double)reinterpret_cast<const float*>(p)[0];
+        y = (double)reinterpret_cast<const float*>(p)[1];
+    }
+    const int64_t g = a.f0 + i;
+    a.feat_uv[2 * g] = x;
+    a.feat_uv[2 * g + 1] = y;
+    a.feat_lm[g] = 0;  // the frame arrives without links (tracking.cpp:577)
+    a.feat_fl[g] = 0;
+    a.winner[i] = INT_MAX;
+    int ok = 0;
+    if (a.has_depth) {
+        D3 pw;
+        if (depth_point(a.dv, x, y, pw)) {
+            a.dpw[3 * i] = pw.x;
+            a.dpw[3 * i + 1] = pw.y;
+            a.dpw[3 * i + 2] = pw.z;
+            ok = 1;
+        }
+    }
+    a.dvalid[i] = ok;
+}
+
+__global__ __launch_bounds__(kThreads) void k_kf_match(KfArgs a) {
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    const int n = clampi(*a.n_matches, a.cap_matches);
+    if (k >= n) return;
+    a.tvalid[k] = 0;
+    const int n2 = clampi(*a.n_feat, a.cap_feat);
+    const vx_match mt = a.m[k];
+    const int qi = mt.query_idx, ti = mt.train_idx;
+    if (qi < 0 || qi >= a.nf_last || ti < 0 || ti >= n2) {
+        atomicOr(a.err, VX_KF_ERR_MATCH_RANGE);
+        return;
+    }
+    if (atomicAdd(&a.qseen[qi], 1) != 0) atomicOr(a.err, VX_KF_ERR_DUP_QUERY);
+    const int64_t g1 = a.f0_last + qi, g2 = a.f0 + ti;
+    // has_landmark of the last keyframe's feature; of the new one: only the depth loop set any
+    if ((a.feat_fl[g1] & 1) || a.dvalid[ti]) return;
+    const double x1 = a.feat_uv[2 * g1], y1 = a.feat_uv[2 * g1 + 1];
+    const double x2 = a.feat_uv[2 * g2], y2 = a.feat_uv[2 * g2 + 1];
+    Pose T1;
+    double c1[4];
+    for (int j = 0; j < 4; ++j) T1.q[j] = a.kf_pose[7 * (int64_t)a.k_last + j];
+    for (int j = 0; j < 3; ++j) T1.t[j] = a.kf_pose[7 * (int64_t)a.k_last + 4 + j];
+    for (int j = 0; j < 4; ++j) c1[j] = a.kf_intr[4 * (int64_t)a.k_last + j];
+    D3 pw;
+    if (!tri_gate(x1, y1, x2, y2, c1, a.intr, T1, a.dv.T, a.min_angle_rad, a.max_err, pw)) return;
+    a.tvalid[k] = 1;
+    a.tpw[3 * k] = pw.x;
+    a.tpw[3 * k + 1] = pw.y;
+    a.tpw[3 * k + 2] = pw.z;
+    atomicMin(&a.winner[ti], k);
+}
+
+// Exclusive rank of this thread's flag among the block's flags (thread order) and their total.
+// Two barriers: the wave counts are read by everyone before the next call rewrites them.
+__device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t b = __ballot(flag);
+    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    if (lane == 0) s_cnt[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        const int v = s_cnt[w];
+        before += w < wave ? v : 0;
+        all += v;
+    }
+    __syncthreads();
+    *total = all;
+    return before + in_wave;
+}
+
+__device__ __forceinline__ void put_obs(const KfArgs& a, int64_t j, int row, uint64_t kf, uint64_t fi) {
+    const int64_t o = a.n_obs0 + j, id = a.n_ids0 + j;
+    a.obs_lm[o] = row;
+    a.obs_kf[o] = kf;
+    a.obs_fi[o] = fi;
+    a.obs_id[o] = id;
+    a.id_row[id] = o;
+}
+
+__device__ __forceinline__ void put_landmark(const KfArgs& a, int j, int kind, int feat_curr, int feat_last,
+                                             const double* pw) {
+    const int64_t row = a.n_lm0 + j;
+    const uint64_t id = a.first_id + (uint64_t)j;
+    a.lm_id[row] = id;
+    a.lm_pos[3 * row] = pw[0];
+    a.lm_pos[3 * row + 1] = pw[1];
+    a.lm_pos[3 * row + 2] = pw[2];
+    a.lm_bad[row] = 0;
+    a.feat_lm[a.f0 + feat_curr] = id;
+    a.feat_fl[a.f0 + feat_curr] = 1;  // has_landmark, not outlier
+    vx_keyframe_landmark r;
+    r.lm_id = id;
+    r.row = (int)row;
+    r.kind = kind;
+    r.feat_curr = feat_curr;
+    r.feat_last = feat_last;
+    r.pw[0] = pw[0];
+    r.pw[1] = pw[1];
+    r.pw[2] = pw[2];
+    a.rec[j] = r;
+}
+
+__global__ void __launch_bounds__(kBlock) k_kf_commit(KfArgs a) {
+    __shared__ int s_cnt[kWaves];
+    const int tid = threadIdx.x;
+    const int nf = clampi(*a.n_feat, a.cap_feat);
+    const int nm = a.has_last ? clampi(*a.n_matches, a.cap_matches) : 0;
+    const int err = *a.err;
+    if (err) {  // validate-then-commit: a rejected call writes the header only
+        if (tid == 0) {
+            vx_keyframe_result h{};
+            h.n_feat = nf;
+            h.n_matches = nm;
+            h.first_landmark_id = h.next_landmark_id = a.first_id;
+            h.error_bits = err;
+            *a.hdr = h;
+        }
+        return;
+    }
+    // 1: CreateLandmarksFromDepth's landmarks, feature order
+    int nd = 0;
+    for (int base = 0; base < nf; base += kBlock) {
+        const int i = base + tid;
+        const bool made = i < nf && a.dvalid[i] != 0;
+        int total;
+        const int r = block_rank(made, s_cnt, &total);
+        if (made) {
+            const int j = nd + r;
+            put_landmark(a, j, 0, i, -1, a.dpw + 3 * (int64_t)i);
+            put_obs(a, j, (int)(a.n_lm0 + j), a.kf_id, (uint64_t)i);
+        }
+        nd += total;
+    }
+    // 2: TriangulateWithLastKeyFrame's, match order; a train feature's first passing match wins
+    int nt = 0;
+    for (int base = 0; base < nm; base += kBlock) {
+        const int k = base + tid;
+        bool made = false;
+        vx_match mt{};
+        if (k < nm && a.tvalid[k]) {  // (tvalid: both indices are in range)
+            mt = a.m[k];
+            made = a.winner[mt.train_idx] == k;
+        }
+        int total;
+        const int r = block_rank(made, s_cnt, &total);
+        if (made) {
+            const int j = nd + nt + r;
+            const int64_t o = (int64_t)nd + 2 * (int64_t)(nt + r);
+            const uint64_t id = a.first_id + (uint64_t)j;
+            put_landmark(a, j, 1, mt.train_idx, mt.query_idx, a.tpw + 3 * (int64_t)k);
+            put_obs(a, o, (int)(a.n_lm0 + j), a.last_kf_id, (uint64_t)mt.query_idx);  // (tracking.cpp:916)
+            put_obs(a, o + 1, (int)(a.n_lm0 + j), a.kf_id, (uint64_t)mt.train_idx);   // (:917)
+            a.feat_lm[a.f0_last + mt.query_idx] = id;
+            a.feat_fl[a.f0_last + mt.query_idx] = 1;
+        }
+        nt += total;
+    }
+    if (tid == 0) {  // Map::InsertKeyFrame's rows and the header
+        for (int j = 0; j < 7; ++j) a.kf_pose[7 * (int64_t)a.k_new + j] = a.pose[j];
+        for (int j = 0; j < 4; ++j) a.kf_intr[4 * (int64_t)a.k_new + j] = a.intr[j];
+        vx_keyframe_result h{};
+        h.n_feat = nf;
+        h.n_depth = nd;
+        h.n_triangulated = nt;
+        h.n_matches = nm;
+        h.first_landmark_id = a.first_id;
+        h.next_landmark_id = a.first_id + (uint64_t)(nd + nt);
+        *a.hdr = h;
+    }
+}
+
+// room for `want` bytes keeping the first `used` (doubling, as the map's edit calls grow); the copy
+// runs on the map context's stream, and no stream may still use the old block when it is freed
+int grow(vx_ctx* c, vx_dmap* m, DevBuf& d, size_t used, size_t want) {
+    if (want <= d.bytes) return VX_OK;
+    size_t cap = std::max<size_t>(d.bytes * 2, 4096);
+    while (cap < want) cap *= 2;
+    void* np = nullptr;
+    VX_HIP(c, hipMalloc(&np, cap));
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(np, d.p, used, hipMemcpyDeviceToDevice, m->c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->c->stream);
+    if (e == hipSuccess && c != m->c) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        return hip_fail(c, e, "growing a map array");
+    }
+    d.release();
+    d.p = np;
+    d.bytes = cap;
+    return VX_OK;
+}
+
+size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+constexpr size_t kRecOff = 64;  // pinned block: vx_keyframe_result | records
+
+int reject(vx_ctx* c, vx_keyframe_result* res, int bits, const char* what) {
+    res->error_bits = bits;
+    return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe: %s", what);
+}
+
+struct Input {
+    const uint8_t* xy;
+    int64_t stride;
+    int xy_f64;
+    const int32_t* n_feat;
+    int cap_feat;
+    const vx_match* matches;
+    const int32_t* n_matches;
+    int cap_matches;
+    const void* depth;
+    int depth_type, rows, cols;
+    int64_t row_stride;
+};
+
+int depth_elem(int type) { return type == VX_DEPTH_U16 ? 2 : (type == VX_DEPTH_F32 ? 4 : 8); }
+
+// the sequence over inputs already on the device, its one synchronisation, then the host mirrors
+int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4, const Input& in,
+               int has_last, uint64_t last_kf_id, uint64_t first_id, const vx_keyframe_options* opt,
+               vx_keyframe_result* res) {
+    auto& K = m->create;
+    K.rec.clear();
+    std::memset(res, 0, sizeof *res);
+    res->first_landmark_id = res->next_landmark_id = first_id;
+    const int cap_feat = in.cap_feat, cap_m = has_last ? in.cap_matches : 0;
+    // what the edit calls refuse, before anything is enqueued
+    int bits = 0, k_last = 0;
+    if (m->kf_index.count(kf_id)) bits |= VX_KF_ERR_KF_LIVE;
+    if (!intr4) bits |= VX_KF_ERR_NO_CAMERA;
+    if (has_last) {
+        const auto it = m->kf_index.find(last_kf_id);
+        if (it == m->kf_index.end()) bits |= VX_KF_ERR_NO_LAST;
+        else if (!m->kf_has_cam[k_last = it->second]) bits |= VX_KF_ERR_NO_CAMERA;
+    }
+    for (int i = 0; i < cap_feat && !(bits & VX_KF_ERR_ID_RANGE); ++i)
+        if (m->lm_index.count(first_id + (uint64_t)i)) bits |= VX_KF_ERR_ID_RANGE;
+    if (bits & VX_KF_ERR_KF_LIVE) return reject(c, res, bits, "the keyframe is already in the map");
+    if (bits & VX_KF_ERR_NO_LAST) return reject(c, res, bits, "the last keyframe is not in the map");
+    if (bits & VX_KF_ERR_NO_CAMERA) return reject(c, res, bits, "a keyframe without a camera");
+    if (bits) return reject(c, res, bits, "a landmark id of the range is already in the map");
+    const bool has_depth = in.depth && in.rows > 0 && in.cols > 0;  // Depth().empty() (tracking.cpp:591-594)
+    if (has_depth) {
+        if (in.depth_type < VX_DEPTH_U16 || in.depth_type > VX_DEPTH_F64)
+            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", in.depth_type);
+        if (in.row_stride < (int64_t)in.cols * depth_elem(in.depth_type))
+            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
+    }
+    VX_HIP(c, hipSetDevice(c->device));
+    const int64_t k = (int64_t)m->kf_id.size(), f0 = m->kf_feat_ptr.back();
+    const int64_t f0_last = has_last ? m->kf_feat_ptr[k_last] : 0;
+    const int nf_last = has_last ? (int)(m->kf_feat_ptr[k_last + 1] - f0_last) : 0;
+    if (m->n_lm + cap_feat > (int64_t)INT_MAX || f0 + cap_feat > (int64_t)INT_MAX)
+        return set_error(c, VX_ERR_CAPACITY, "the map's rows would pass 2^31");
+    // the worst case: every feature linked, every link a triangulated landmark's (two observations)
+    int rc;
+    const size_t cf = (size_t)cap_feat;
+    if ((rc = grow(c, m, m->kf_pose, (size_t)k * 56, (size_t)(k + 1) * 56))) return rc;
+    if ((rc = grow(c, m, m->kf_intr, (size_t)k * 32, (size_t)(k + 1) * 32))) return rc;
+    if ((rc = grow(c, m, m->feat_uv, (size_t)f0 * 16, ((size_t)f0 + cf) * 16))) return rc;
+    if ((rc = grow(c, m, m->feat_lm, (size_t)f0 * 8, ((size_t)f0 + cf) * 8))) return rc;
+    if ((rc = grow(c, m, m->feat_fl, (size_t)f0, (size_t)f0 + cf))) return rc;
+    if ((rc = grow(c, m, m->lm_id, (size_t)m->n_lm * 8, ((size_t)m->n_lm + cf) * 8))) return rc;
+    if ((rc = grow(c, m, m->lm_pos, (size_t)m->n_lm * 24, ((size_t)m->n_lm + cf) * 24))) return rc;
+    if ((rc = grow(c, m, m->lm_bad, (size_t)m->n_lm, (size_t)m->n_lm + cf))) return rc;
+    if ((rc = grow(c, m, m->obs_lm, (size_t)m->n_obs * 4, ((size_t)m->n_obs + 2 * cf) * 4))) return rc;
+    if ((rc = grow(c, m, m->obs_kf, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
+    if ((rc = grow(c, m, m->obs_fi, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
+    if ((rc = grow(c, m, m->obs_id, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
+    if ((rc = grow(c, m, m->id_row, (size_t)m->n_ids * 8, ((size_t)m->n_ids + 2 * cf) * 8))) return rc;
+    VX_HIP(c, K.dvalid.ensure(std::max<size_t>(cf, 1) * sizeof(int)));
+    VX_HIP(c, K.dpw.ensure(std::max<size_t>(cf, 1) * 3 * sizeof(double)));
+    VX_HIP(c, K.tvalid.ensure((size_t)std::max(cap_m, 1) * sizeof(int)));
+    VX_HIP(c, K.tpw.ensure((size_t)std::max(cap_m, 1) * 3 * sizeof(double)));
+    VX_HIP(c, K.aux.ensure((cf + (size_t)nf_last + 4) * sizeof(int)));
+    VX_HIP(c, K.host.ensure(kRecOff + std::max<size_t>(cf, 1) * sizeof(vx_keyframe_landmark)));
+    if (m->c != c && (rc = vx_stream_wait_ctx(c, m->c))) return rc;
+
+    KfArgs a{};
+    a.kf_id = kf_id;
+    a.last_kf_id = last_kf_id;
+    a.first_id = first_id;
+    a.xy = in.xy;
+    a.stride = in.stride;
+    a.xy_f64 = in.xy_f64;
+    a.n_feat = in.n_feat;
+    a.cap_feat = cap_feat;
+    a.has_depth = has_depth ? 1 : 0;
+    a.dv.depth = static_cast<const uint8_t*>(in.depth);
+    a.dv.type = in.depth_type;
+    a.dv.rows = in.rows;
+    a.dv.cols = in.cols;
+    a.dv.stride = in.row_stride;
+    a.dv.fx = intr4[0];
+    a.dv.fy = intr4[1];
+    a.dv.cx = intr4[2];
+    a.dv.cy = intr4[3];
+    for (int j = 0; j < 4; ++j) a.dv.T.q[j] = pose7[j];
+    for (int j = 0; j < 3; ++j) a.dv.T.t[j] = pose7[4 + j];
+    a.has_last = has_last ? 1 : 0;
+    a.k_last = k_last;
+    a.nf_last = nf_last;
+    a.f0_last = f0_last;
+    a.m = in.matches;
+    a.n_matches = in.n_matches;
+    a.cap_matches = cap_m;
+    a.min_angle_rad = opt->tri_min_angle_deg * M_PI / 180.0;  // tracking.cpp:870-871
+    a.max_err = opt->tri_max_reproj_error;
+    a.kf_pose = m->kf_pose.as<double>();
+    a.kf_intr = m->kf_intr.as<double>();
+    a.feat_uv = m->feat_uv.as<double>();
+    a.feat_lm = m->feat_lm.as<uint64_t>();
+    a.feat_fl = m->feat_fl.as<uint8_t>();
+    a.lm_id = m->lm_id.as<uint64_t>();
+    a.lm_pos = m->lm_pos.as<double>();
+    a.lm_bad = m->lm_bad.as<uint8_t>();
+    a.obs_lm = m->obs_lm.as<int>();
+    a.obs_kf = m->obs_kf.as<uint64_t>();
+    a.obs_fi = m->obs_fi.as<uint64_t>();
+    a.obs_id = m->obs_id.as<int64_t>();
+    a.id_row = m->id_row.as<int64_t>();
+    a.k_new = (int)k;
+    a.f0 = f0;
+    a.n_lm0 = m->n_lm;
+    a.n_obs0 = m->n_obs;
+    a.n_ids0 = m->n_ids;
+    for (int j = 0; j < 7; ++j) a.pose[j] = pose7[j];
+    for (int j = 0; j < 4; ++j) a.intr[j] = intr4[j];
+    a.dvalid = K.dvalid.as<int>();
+    a.dpw = K.dpw.as<double>();
+    a.tvalid = K.tvalid.as<int>();
+    a.tpw = K.tpw.as<double>();
+    a.winner = K.aux.as<int>();
+    a.qseen = a.winner + cap_feat;
+    a.err = a.qseen + nf_last;
+    uint8_t* H = static_cast<uint8_t*>(K.host.p);
+    a.hdr = reinterpret_cast<vx_keyframe_result*>(H);
+    a.rec = reinterpret_cast<vx_keyframe_landmark*>(H + kRecOff);
+
+    VX_HIP(c, hipMemsetAsync(a.qseen, 0, ((size_t)nf_last + 1) * sizeof(int), c->stream));
+    VX_HIP(c, launch(c, kStKfFeat, k_kf_feat, dim3(std::max(1, (cap_feat + kThreads - 1) / kThreads)), dim3(kThreads),
+                     0, c->stream, a));
+    if (has_last)
+        VX_HIP(c, launch(c, kStKfMatch, k_kf_match, dim3(std::max(1, (cap_m + kThreads - 1) / kThreads)),
+                         dim3(kThreads), 0, c->stream, a));
+    VX_HIP(c, launch(c, kStKfCommit, k_kf_commit, dim3(1), dim3(kBlock), 0, c->stream, a));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) prof_collect(c);
+
+    std::memcpy(res, H, sizeof *res);
+    if (res->error_bits) {
+        if (res->error_bits & VX_KF_ERR_MATCH_RANGE) return set_error(c, VX_ERR_INVALID, "match index out of range");
+        return set_error(c, VX_ERR_INVALID, "duplicate query index (matches must come from one knnMatch)");
+    }
+    const int nf = res->n_feat, nd = res->n_depth, nt = res->n_triangulated, n_new = nd + nt;
+    if (nf < 0 || nf > cap_feat || nd < 0 || nt < 0 || n_new > nf)
+        return set_error(c, VX_ERR_STATE, "keyframe creation: %d depth + %d triangulated landmarks for %d features", nd,
+                         nt, nf);
+    // the host mirrors, as vx_dmap_add_landmarks / add_observations / set_features / add_keyframe leave them
+    K.rec.resize(n_new);
+    if (n_new) std::memcpy(K.rec.data(), H + kRecOff, (size_t)n_new * sizeof(vx_keyframe_landmark));
+    m->lm_obs_live.resize(m->n_lm + n_new, 0);
+    m->lm_removed.resize(m->n_lm + n_new, 0);
+    m->feat_flags.resize((size_t)f0 + nf, 0);
+    int64_t oid = m->n_ids;
+    for (const vx_keyframe_landmark& r : K.rec) {
+        m->lm_index[r.lm_id] = r.row;
+        if (r.kind == 1) {
+            m->obs_index.emplace(std::make_pair((int)r.row, last_kf_id), oid++);
+            const int64_t g = f0_last + r.feat_last;
+            m->kf_valid_cnt[k_last] += 1 - (m->feat_flags[g] & 1);
+            m->feat_flags[g] = 1;
+        }
+        m->obs_index.emplace(std::make_pair((int)r.row, kf_id), oid++);
+        m->lm_obs_live[r.row] = r.kind == 1 ? 2 : 1;
+        m->feat_flags[f0 + r.feat_curr] = 1;
+    }
+    const int64_t n_obs_new = (int64_t)nd + 2 * (int64_t)nt;
+    m->n_lm += n_new;
+    m->n_lm_live += n_new;
+    m->n_obs += n_obs_new;
+    m->n_ids += n_obs_new;
+    m->n_obs_live += n_obs_new;
+    if (n_new) m->csr_dirty = true;
+    m->kf_index[kf_id] = (int)k;
+    m->kf_id.push_back(kf_id);
+    m->kf_feat_ptr.push_back(f0 + nf);
+    m->kf_has_cam.push_back(1);
+    m->kf_alive.push_back(1);
+    ++m->n_kf_live;
+    m->kf_valid_cnt.push_back(n_new);
+    return VX_OK;
+}
+
+int check_common(vx_ctx* c, const vx_dmap* m, const double* pose7, const vx_keyframe_options* opt,
+                 const vx_keyframe_result* res, const char* who) {
+    if (!m || !m->c || !pose7 || !opt || !res) return set_error(c, VX_ERR_INVALID, "%s: null argument", who);
+    if (m->c->device != c->device) return set_error(c, VX_ERR_INVALID, "map and context on different devices");
+    if (!(opt->tri_min_angle_deg == opt->tri_min_angle_deg) || !(opt->tri_max_reproj_error == opt->tri_max_reproj_error))
+        return set_error(c, VX_ERR_INVALID, "%s: NaN option", who);
+    return VX_OK;
+}
+
+}  // namespace
+}  // namespace vx
+
+using namespace vx;
+
+extern "C" {
+
+void vx_keyframe_default_options(vx_keyframe_options* o) {
+    if (!o) return;
+    o->tri_min_angle_deg = 1.0;      // Tracking::Options (tracking.h:43-44)
+    o->tri_max_reproj_error = 5.0;
+}
+
+int vx_keyframe_block(void) { return kBlock; }
+
+int vx_dmap_create_keyframe(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4,
+                            const float* d_xy, int64_t stride_bytes, const int32_t* d_n_feat, int cap_feat,
+                            int has_last, uint64_t last_kf_id, const vx_match* d_matches,
+                            const int32_t* d_n_matches, int cap_matches, const void* d_depth, int depth_type,
+                            int rows, int cols, int64_t row_stride, uint64_t first_landmark_id,
+                            const vx_keyframe_options* opt, vx_keyframe_result* result) {
+    if (!c) return VX_ERR_INVALID;
+    int rc;
+    if ((rc = check_common(c, m, pose7, opt, result, "vx_dmap_create_keyframe"))) return rc;
+    if (!d_n_feat || cap_feat < 0 || (cap_feat > 0 && !d_xy))
+        return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe: feature rows without a count / capacity");
+    if (stride_bytes < 8 || (stride_bytes & 3))
+        return set_error(c, VX_ERR_INVALID, "position stride %lld: a multiple of 4, at least 8", (long long)stride_bytes);
+    if (has_last) {
+        if (d_matches) {
+            if (!d_n_matches || cap_matches < 0)
+                return set_error(c, VX_ERR_INVALID, "match list without a count / capacity");
+        } else {
+            if (!c->match_valid) return set_error(c, VX_ERR_STATE, "no match enqueued on this context");
+            d_matches = c->matches.as<vx_match>();
+            d_n_matches = c->match_count.as<int32_t>();
+            cap_matches = c->match_cap;
+        }
+    }
+    Input in{};
+    in.xy = reinterpret_cast<const uint8_t*>(d_xy);
+    in.stride = stride_bytes;
+    in.xy_f64 = 0;
+    in.n_feat = d_n_feat;
+    in.cap_feat = cap_feat;
+    in.matches = d_matches;
+    in.n_matches = d_n_matches;
+    in.cap_matches = cap_matches;
+    in.depth = d_depth;
+    in.depth_type = depth_type;
+    in.rows = rows;
+    in.cols = cols;
+    in.row_stride = row_stride;
+    return create_run(c, m, kf_id, pose7, intr4, in, has_last, last_kf_id, first_landmark_id, opt, result);
+}
+
+int vx_dmap_create_keyframe_host(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4,
+                                 const double* feat_uv, int n_feat, int has_last, uint64_t last_kf_id,
+                                 const vx_match* matches, int n_matches, const void* depth, int depth_type, int rows,
+                                 int cols, int64_t row_stride, uint64_t first_landmark_id,
+                                 const vx_keyframe_options* opt, vx_keyframe_result* result) {
+    if (!c) return VX_ERR_INVALID;
+    int rc;
+    if ((rc = check_common(c, m, pose7, opt, result, "vx_dmap_create_keyframe_host"))) return rc;
+    if (n_feat < 0 || (n_feat > 0 && !feat_uv) || n_matches < 0 || (has_last && n_matches > 0 && !matches))
+        return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe_host: bad feature / match arguments");
+    const bool has_depth = depth && rows > 0 && cols > 0;
+    if (has_depth) {
+        if (depth_type < VX_DEPTH_U16 || depth_type > VX_DEPTH_F64)
+            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", depth_type);
+        if (row_stride < (int64_t)cols * depth_elem(depth_type))
+            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
+    }
+    VX_HIP(c, hipSetDevice(c->device));
+    auto& K = m->create;
+    // one staged block: {n_feat, n_matches} | positions | matches | depth image
+    const int nm = has_last ? n_matches : 0;
+    const size_t o_uv = 64, o_m = align64(o_uv + (size_t)n_feat * 16), o_d = align64(o_m + (size_t)nm * sizeof(vx_match)),
+                 d_bytes = has_depth ? (size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(depth_type) : 0, bytes = align64(o_d + d_bytes);
+    // (the one place this entry can block: until the previous call's upload has left the staging)
+    if (K.in_event) VX_HIP(c, hipEventSynchronize(K.in_event));
+    else VX_HIP(c, hipEventCreateWithFlags(&K.in_event, hipEventDisableTiming));
+    VX_HIP(c, K.in_host.ensure(bytes));
+    VX_HIP(c, K.in.ensure(bytes));
+    uint8_t* h = static_cast<uint8_t*>(K.in_host.p);
+    const int32_t counts[4] = {n_feat, nm, 0, 0};
+    std::memcpy(h, counts, sizeof counts);
+    if (n_feat) std::memcpy(h + o_uv, feat_uv, (size_t)n_feat * 16);
+    if (nm) std::memcpy(h + o_m, matches, (size_t)nm * sizeof(vx_match));
+    if (d_bytes) std::memcpy(h + o_d, depth, d_bytes);
+    VX_HIP(c, hipMemcpyAsync(K.in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
+    VX_HIP(c, hipEventRecord(K.in_event, c->stream));
+    const uint8_t* d = K.in.as<uint8_t>();
+    Input in{};
+    in.xy = d + o_uv;
+    in.stride = 16;
+    in.xy_f64 = 1;
+    in.n_feat = K.in.as<int32_t>();
+    in.cap_feat = n_feat;
+    in.matches = reinterpret_cast<const vx_match*>(d + o_m);
+    in.n_matches = K.in.as<int32_t>() + 1;
+    in.cap_matches = nm;
+    in.depth = has_depth ? d + o_d : nullptr;
+    in.depth_type = depth_type;
+    in.rows = rows;
+    in.cols = cols;
+    in.row_stride = row_stride;
+    return create_run(c, m, kf_id, pose7, intr4, in, has_last, last_kf_id, first_landmark_id, opt, result);
+}
+
+int vx_dmap_create_results(vx_dmap* m, int cap, vx_keyframe_landmark* records, int* n) {
+    if (!m) return VX_ERR_INVALID;
+    const auto& R = m->create.rec;
+    const int k = (int)R.size();
+    if (n) *n = k;
+    if (records && k > cap) return set_error(m->c, VX_ERR_CAPACITY, "need %d landmark records, cap %d", k, cap);
+    if (records && k) std::memcpy(records, R.data(), (size_t)k * sizeof(vx_keyframe_landmark));
+    return VX_OK;
+}
+
+int vx_dmap_keyframe_features(vx_dmap* m, uint64_t kf_id, int cap, double* uv, uint64_t* lm_id, uint8_t* flags,
+                              int* n) {
+    if (!m) return VX_ERR_INVALID;
+    vx_ctx* c = m->c;
+    const auto it = m->kf_index.find(kf_id);
+    if (it == m->kf_index.end())
+        return set_error(c, VX_ERR_INVALID, "keyframe %llu is not in the map", (unsigned long long)kf_id);
+    const int64_t f0 = m->kf_feat_ptr[it->second];
+    const int nf = (int)(m->kf_feat_ptr[it->second + 1] - f0);
+    if (n) *n = nf;
+    if ((uv || lm_id || flags) && nf > cap) return set_error(c, VX_ERR_CAPACITY, "need %d features, cap %d", nf, cap);
+    if (!nf) return VX_OK;
+    VX_HIP(c, hipSetDevice(c->device));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (uv) VX_HIP(c, hipMemcpy(uv, m->feat_uv.as<double>() + 2 * f0, (size_t)nf * 16, hipMemcpyDeviceToHost));
+    if (lm_id) VX_HIP(c, hipMemcpy(lm_id, m->feat_lm.as<uint64_t>() + f0, (size_t)nf * 8, hipMemcpyDeviceToHost));
+    if (flags) VX_HIP(c, hipMemcpy(flags, m->feat_fl.as<uint8_t>() + f0, (size_t)nf, hipMemcpyDeviceToHost));
+    return VX_OK;
+}
+
+}  // extern "C"
+
+static_assert(sizeof(vx_keyframe_options) == 16, "vx_keyframe_options layout (python KEYFRAME_OPTIONS_DTYPE)");
+static_assert(sizeof(vx_keyframe_result) == 40, "vx_keyframe_result layout (python KEYFRAME_RESULT_DTYPE)");
+static_assert(sizeof(vx_keyframe_landmark) == 48, "vx_keyframe_landmark layout (python KEYFRAME_LANDMARK_DTYPE)");

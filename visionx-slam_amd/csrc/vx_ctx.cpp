@@ -172,7 +172,7 @@ static const char* kStageNames[vx::kStCount] = {
     "sba_landmark",   "sba_blocks",    "sba_solve",       "sba_update",     "sba_allreduce",
     "lm_depth",       "lm_triangulate", "lm_compact",  "pnp_hypotheses", "pnp_refine",
     "em_hypotheses",  "em_select",     "ba_iter",         "ba_prologue",
-    "ba_window",      "track_pairs"};
+    "ba_window",      "track_pairs",   "kf_features",     "kf_matches",  "kf_commit"};
 
 extern "C" {
 
@@ -345,16 +345,19 @@ void vx_event_destroy(vx_event* e) {
     delete e;
 }
 
-int vx_prof_enable(vx_ctx* c, int mask) {
+int vx_prof_enable64(vx_ctx* c, uint64_t mask) {
     if (!c) return VX_ERR_INVALID;
     if (!mask) {
         (void)hipStreamSynchronize(c->stream);
         vx::prof_collect(c);
     }
     c->prof = mask != 0;
-    c->prof_mask = (unsigned)mask;
+    c->prof_mask = mask;
     return VX_OK;
 }
+
+// (the int mask sign-extends: -1 is every stage; stages 32 and up need vx_prof_enable64)
+int vx_prof_enable(vx_ctx* c, int mask) { return vx_prof_enable64(c, (uint64_t)(int64_t)mask); }
 
 int vx_prof_count(void) { return vx::kStCount; }
 

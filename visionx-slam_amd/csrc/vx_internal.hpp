@@ -67,6 +67,9 @@ enum Stage : int {
     kStBaPrologue,    // iteration 0's pose stage of the fused path
     kStBaWin,         // the whole LocalBA window in one persistent launch (k_ba_win)
     kStTrackPairs,    // TrackWithPnP's filter + pair gather (k_track_pairs)
+    kStKfFeat,        // CreateKeyFrame on the resident map: feature rows + depth (k_kf_feat)
+    kStKfMatch,       // its triangulation gate per match (k_kf_match)
+    kStKfCommit,      // its ordered compactions and the map edit (k_kf_commit)
     kStCount
 };
 
@@ -255,7 +258,7 @@ struct vx_ctx {
 
     // ---- profiling
     bool prof = false;
-    unsigned prof_mask = 0;
+    uint64_t prof_mask = 0;
     std::vector<vx::ProfEvent> pending;
     std::vector<hipEvent_t> event_pool;
     double prof_ms[vx::kStCount] = {0};

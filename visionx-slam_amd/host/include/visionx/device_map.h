@@ -57,6 +57,10 @@ public:
     void DroppedLandmark(int64_t row, uint64_t lm_id);
     void DroppedKeyFrame(uint64_t kf_id);
 
+    // after an insertion the resident map made itself (vx_dmap_create_keyframe*, mapping.h): the new
+    // landmarks (in row order, the first at row `first_row`) and the new keyframe enter the row tables
+    void Created(int64_t first_row, const std::vector<Landmark::Ptr>& lms, const Frame::Ptr& kf);
+
     // queued edits to the device (Optimize does this itself)
     void Flush();
     vx_dmap* handle() { return dm_; }

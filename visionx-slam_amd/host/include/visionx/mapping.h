@@ -5,6 +5,11 @@
 //   TriangulateWithLastKeyFrame  tracking.cpp:856-929   -> Match() + vx_triangulate
 //   (TriangulatePoint / ProjectionMatrix, tracking.cpp:843-854, 931-945, run inside the kernel)
 //
+// With a DeviceMap (UseDeviceMap) the whole block of tracking.cpp:577-581 — both functions and
+// Map::InsertKeyFrame — is one call on the resident map:
+//
+//   CreateKeyFrame(last, curr)   tracking.cpp:577-581   -> Match() + vx_dmap_create_keyframe_host
+//
 // Same member names, option names / defaults (Tracking::Options, tracking.h:43-44) and side effects
 // as the reference: landmarks get consecutive ids from landmark_id_, observations are added and
 // the features' landmark_id_ / has_landmark / is_outlier are set in the reference's order.
@@ -29,6 +34,18 @@ public:
     void CreateLandmarksFromDepth(const Frame::Ptr& frame);
     void TriangulateWithLastKeyFrame(Frame::Ptr last_frame, Frame::Ptr curr_frame);
 
+    // The resident map CreateKeyFrame works on (device_map.h); it must already mirror map_.
+    void UseDeviceMap(std::shared_ptr<DeviceMap> dm) { dmap_ = std::move(dm); }
+    // CreateLandmarksFromDepth(curr) + TriangulateWithLastKeyFrame(last, curr) + Map::InsertKeyFrame(curr)
+    // (+ DeviceMap::InsertKeyFrame) as one vx_dmap_create_keyframe_host call: the decision and the
+    // resident map's edit run on the device — the last keyframe's pose is the resident one, which
+    // after a LocalBA may be ahead of last_frame->Pose() — and the reference's loop bodies then run
+    // over the returned records on the host objects; nothing is forwarded to the device a second
+    // time.  curr arrives without links (tracking.cpp:577); last_frame may be null (the first frame
+    // of InitWithSecondFrame: no triangulation).  Returns the next landmark_id_.
+    uint64_t CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr curr_frame);
+    const std::vector<vx_keyframe_landmark>& LastRecords() const { return rec_; }
+
     uint64_t landmark_id_ = 0;  // Tracking::landmark_id_ (tracking.h): next landmark id
 
 private:
@@ -39,6 +56,8 @@ private:
     std::vector<uint8_t> has_, has2_;
     std::vector<int32_t> idx_;
     std::vector<vx_match> m_;
+    std::shared_ptr<DeviceMap> dmap_;
+    std::vector<vx_keyframe_landmark> rec_;
 };
 
 }  // namespace visionx

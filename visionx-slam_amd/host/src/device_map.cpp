@@ -132,6 +132,17 @@ void DeviceMap::DroppedKeyFrame(uint64_t kf_id) {
     kf_row_.erase(it);
 }
 
+void DeviceMap::Created(int64_t first_row, const std::vector<Landmark::Ptr>& lms, const Frame::Ptr& kf) {
+    if (!lms.empty() && first_row != (int64_t)landmarks_.size())
+        throw std::runtime_error("DeviceMap::Created: the resident landmark rows and the row table disagree");
+    for (const auto& l : lms) {
+        lm_row_[l->Id()] = (int64_t)landmarks_.size();
+        landmarks_.push_back(l);
+    }
+    kf_row_[kf->Id()] = (int64_t)frames_.size();
+    frames_.push_back(kf);
+}
+
 void DeviceMap::SetBad(uint64_t lm_id, bool bad) {
     Flush();
     const uint8_t b = bad ? 1 : 0;

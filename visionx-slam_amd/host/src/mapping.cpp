@@ -1,6 +1,8 @@
 // mapping.cpp — KeyFrameLandmarks over vx_depth_landmarks / vx_triangulate (see mapping.h).
 #include "visionx/mapping.h"
 
+#include "visionx/device_map.h"
+
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -116,6 +118,64 @@ void KeyFrameLandmarks::TriangulateWithLastKeyFrame(Frame::Ptr last_frame, Frame
         f2[m.trainIdx].has_landmark = true;
         f2[m.trainIdx].is_outlier = false;
     }
+}
+
+// tracking.cpp:577-581 on the resident map
+uint64_t KeyFrameLandmarks::CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr curr_frame) {
+    if (!dmap_) throw std::runtime_error("KeyFrameLandmarks::CreateKeyFrame: no DeviceMap (UseDeviceMap)");
+    if (!map_ || !curr_frame) return landmark_id_;
+    const auto cam = curr_frame->GetCamera();
+    if (!cam) throw std::runtime_error("KeyFrameLandmarks::CreateKeyFrame: the frame has no camera");
+    std::vector<DMatch> matches;
+    if (last_frame) matcher_->Match(last_frame, curr_frame, matches);
+    auto& f2 = curr_frame->Features();
+    const int n = (int)f2.size(), nm = (int)matches.size();
+    uv_.resize(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        uv_[2 * i] = f2[i].position.x;
+        uv_[2 * i + 1] = f2[i].position.y;
+    }
+    m_.resize(nm);
+    for (int k = 0; k < nm; ++k) m_[k] = vx_match{matches[k].queryIdx, matches[k].trainIdx, matches[k].distance};
+    const double intr[4] = {cam->fx(), cam->fy(), cam->cx(), cam->cy()};
+    double T[7];
+    pose7(curr_frame->Pose(), T);
+    const DepthImage& depth = curr_frame->Depth();
+    const vx_keyframe_options o{options_.triangulation_min_angle_deg, options_.triangulation_max_reproj_error};
+    dmap_->Flush();  // queued edits first: the call reads the resident map
+    vx_ctx* c = dmap_->context();
+    vx_keyframe_result res{};
+    check(c, vx_dmap_create_keyframe_host(c, dmap_->handle(), curr_frame->Id(), T, intr, uv_.data(), n,
+                                          last_frame ? 1 : 0, last_frame ? last_frame->Id() : 0, m_.data(), nm,
+                                          depth.empty() ? nullptr : depth.ptr(), depth.type, depth.rows, depth.cols,
+                                          (int64_t)depth.step, landmark_id_, &o, &res),
+          "vx_dmap_create_keyframe_host");
+    int n_rec = 0;
+    rec_.resize((size_t)res.n_depth + (size_t)res.n_triangulated);
+    check(c, vx_dmap_create_results(dmap_->handle(), (int)rec_.size(), rec_.data(), &n_rec), "vx_dmap_create_results");
+    std::vector<Landmark::Ptr> made;
+    made.reserve(rec_.size());
+    for (const vx_keyframe_landmark& r : rec_) {  // the loop bodies of tracking.cpp:634-643 and :915-925
+        auto lm = std::make_shared<Landmark>(r.lm_id, Vec3d(r.pw[0], r.pw[1], r.pw[2]));
+        if (r.kind == 1) {
+            lm->AddObservation(last_frame->Id(), (size_t)r.feat_last);
+            Feature& a = last_frame->Features()[(size_t)r.feat_last];
+            a.landmark_id_ = lm->Id();
+            a.has_landmark = true;
+            a.is_outlier = false;
+        }
+        lm->AddObservation(curr_frame->Id(), (size_t)r.feat_curr);
+        map_->InsertLandmark(lm);
+        Feature& b = f2[(size_t)r.feat_curr];
+        b.landmark_id_ = lm->Id();
+        b.has_landmark = true;
+        b.is_outlier = false;
+        made.push_back(std::move(lm));
+    }
+    map_->InsertKeyFrame(curr_frame);  // tracking.cpp:581
+    dmap_->Created(rec_.empty() ? 0 : rec_.front().row, made, curr_frame);
+    landmark_id_ = res.next_landmark_id;
+    return landmark_id_;
 }
 
 }  // namespace visionx

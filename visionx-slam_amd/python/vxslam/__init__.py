@@ -99,6 +99,8 @@ EXPORTS = [
     "vx_track_default_options", "vx_orb_slot_keypoints", "vx_track_pnp_async", "vx_track_pnp_fetch", "vx_track_block", "vx_track_pnp_host_async",
     "vx_cull_default_options", "vx_dmap_cull_landmarks", "vx_dmap_keyframe_redundancy", "vx_dmap_cull_keyframes",
     "vx_dmap_cull_results", "vx_cull_block", "vx_cull_lds_keyframes",
+    "vx_keyframe_default_options", "vx_dmap_create_keyframe", "vx_dmap_create_keyframe_host", "vx_dmap_create_results",
+    "vx_dmap_keyframe_features", "vx_keyframe_block", "vx_prof_enable64",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -198,6 +200,20 @@ def lib():
                                              C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.vx_dmap_cull_results.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]
+        L.vx_prof_enable64.argtypes = [C.c_void_p, C.c_uint64]
+        L.vx_keyframe_default_options.restype = None
+        L.vx_keyframe_default_options.argtypes = [C.c_void_p]
+        L.vx_dmap_create_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                              C.c_uint64, C.c_void_p, C.c_void_p]
+        L.vx_dmap_create_keyframe_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint64,
+                                                   C.c_void_p, C.c_void_p]
+        L.vx_dmap_create_results.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        L.vx_dmap_keyframe_features.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int)]
         L.vx_ba_shard_of.restype = C.c_uint32
         L.vx_ba_shard_of.argtypes = [C.c_uint64, C.c_int]
         _lib = L
@@ -305,6 +321,33 @@ def cull_block() -> int:
 def cull_lds_keyframes() -> int:
     """live keyframes up to which the landmark scan holds its keyframe table in LDS"""
     return int(lib().vx_cull_lds_keyframes())
+
+
+# vx_keyframe_options / vx_keyframe_result / vx_keyframe_landmark (include/vx_slam.h; sizes pinned in csrc/keyframe.hip)
+KEYFRAME_OPTIONS_DTYPE = np.dtype([("tri_min_angle_deg", "<f8"), ("tri_max_reproj_error", "<f8")])
+KEYFRAME_RESULT_DTYPE = np.dtype([("n_feat", "<i4"), ("n_depth", "<i4"), ("n_triangulated", "<i4"), ("n_matches", "<i4"),
+                                  ("first_landmark_id", "<u8"), ("next_landmark_id", "<u8"), ("error_bits", "<i4"),
+                                  ("reserved", "<i4")])
+KEYFRAME_LANDMARK_DTYPE = np.dtype([("lm_id", "<u8"), ("row", "<i4"), ("kind", "<i4"), ("feat_curr", "<i4"),
+                                    ("feat_last", "<i4"), ("pw", "<f8", 3)])
+KF_ERR_MATCH_RANGE, KF_ERR_DUP_QUERY, KF_ERR_KF_LIVE, KF_ERR_NO_LAST, KF_ERR_NO_CAMERA, KF_ERR_ID_RANGE = 1, 2, 4, 8, 16, 32
+
+
+def keyframe_options(**fields):
+    """Tracking::Options' triangulation fields (tracking.h:43-44) with the reference's defaults, either
+    overridable by name."""
+    o = np.zeros((), KEYFRAME_OPTIONS_DTYPE)
+    lib().vx_keyframe_default_options(_p(o))
+    for k, v in fields.items():
+        if k not in KEYFRAME_OPTIONS_DTYPE.names:
+            raise TypeError(f"keyframe_options: unknown field {k!r}")
+        o[k] = v
+    return o
+
+
+def keyframe_block() -> int:
+    """threads of the keyframe commit workgroup (the chunk of its two ordered compactions)"""
+    return int(lib().vx_keyframe_block())
 
 
 def track_block() -> int:
@@ -818,7 +861,7 @@ class Context:
             mask = 0
             for s in stages:
                 mask |= 1 << names.index(s)
-        self._check(lib().vx_prof_enable(self._h, mask))
+        self._check(lib().vx_prof_enable64(self._h, C.c_uint64(mask & 0xFFFFFFFFFFFFFFFF)))
 
     def prof_read(self, reset=True) -> dict:
         n = lib().vx_prof_count()
@@ -1118,6 +1161,87 @@ class DMap:
         l_rows = np.ctypeslib.as_array(lr, (m,)).astype(np.int64)
         l_pos = np.ctypeslib.as_array(lp, (m, 4))[:, :3].copy()
         return k_rows, k_pose, l_rows, l_pos
+
+    def _create_done(self, c, rc, res):
+        self.last_create = res[0].copy()
+        c._check(rc)
+        return {"result": res[0], "landmarks": self.create_results()}
+
+    def create_keyframe(self, kf_id, pose7, intr4, curr, *, last_kf_id=None, matches=None, depth=None,
+                        first_landmark_id=0, opts=None, ctx=None):
+        """vx_dmap_create_keyframe: Tracking::CreateKeyFrame (tracking.cpp:577-584) on the resident map
+        from device inputs, one synchronisation.  curr: an extraction slot of the context, or (device
+        pointer of the first x, row stride in bytes, device pointer of the int32 row count, row
+        capacity); last_kf_id None = no triangulation; matches: None = the context's last match_*_async
+        result, or (device pointer of MATCH_DTYPE rows, device pointer of the int32 count, capacity);
+        depth: None, or (device pointer, VX_DEPTH_* type, rows, cols, row stride in bytes).  Returns
+        {"result": KEYFRAME_RESULT_DTYPE record, "landmarks": KEYFRAME_LANDMARK_DTYPE records}; a
+        rejected call raises VxError, its record (error_bits) is self.last_create."""
+        c = self.ctx if ctx is None else ctx
+        if isinstance(curr, (int, np.integer)):
+            _, n_ptr, cap = c.slot_device(int(curr))
+            curr = (c.slot_keypoints(int(curr)), KEYPOINT_DTYPE.itemsize, n_ptr, cap)
+        xy, stride, n_ptr, cap = curr
+        m_ptr, mn_ptr, m_cap = matches if matches is not None else (None, None, 0)
+        d_ptr, d_type, rows, cols, d_stride = depth if depth is not None else (None, 0, 0, 0, 0)
+        pose = np.ascontiguousarray(pose7, np.float64)
+        intr = None if intr4 is None else np.ascontiguousarray(intr4, np.float64)
+        o = np.ascontiguousarray(keyframe_options() if opts is None else opts, KEYFRAME_OPTIONS_DTYPE)
+        res = np.zeros(1, KEYFRAME_RESULT_DTYPE)
+        rc = lib().vx_dmap_create_keyframe(c.handle, self._h, C.c_uint64(int(kf_id)), _p(pose),
+                                           None if intr is None else _p(intr), C.c_void_p(xy), int(stride),
+                                           C.c_void_p(n_ptr), int(cap), 0 if last_kf_id is None else 1,
+                                           C.c_uint64(0 if last_kf_id is None else int(last_kf_id)), C.c_void_p(m_ptr),
+                                           C.c_void_p(mn_ptr), int(m_cap), C.c_void_p(d_ptr), int(d_type), int(rows),
+                                           int(cols), int(d_stride), C.c_uint64(int(first_landmark_id)), _p(o), _p(res))
+        return self._create_done(c, rc, res)
+
+    def create_keyframe_host(self, kf_id, pose7, intr4, feat_uv, *, last_kf_id=None, matches=None, depth=None,
+                             first_landmark_id=0, opts=None, ctx=None):
+        """vx_dmap_create_keyframe_host: the same from host arrays (positions (n, 2) float64, a
+        MATCH_DTYPE list, a 2-D depth image whose row stride is taken from the array), staged and
+        uploaded in one copy.  Returns what create_keyframe returns."""
+        c = self.ctx if ctx is None else ctx
+        uv = np.ascontiguousarray(feat_uv, np.float64).reshape(-1, 2)
+        mt = np.zeros(0, MATCH_DTYPE) if matches is None else np.ascontiguousarray(matches, MATCH_DTYPE)
+        if depth is None:
+            dptr, dt, rows, cols, dstride = None, 0, 0, 0, 0
+        else:
+            if depth.strides[1] != depth.itemsize or depth.strides[0] < depth.shape[1] * depth.itemsize:
+                depth = np.ascontiguousarray(depth)
+            # (a view with padded rows: the rows the call reads end inside its base buffer)
+            dptr, dt = C.c_void_p(depth.ctypes.data), DEPTH_TYPES[depth.dtype]
+            rows, cols, dstride = depth.shape[0], depth.shape[1], depth.strides[0]
+        pose = np.ascontiguousarray(pose7, np.float64)
+        intr = None if intr4 is None else np.ascontiguousarray(intr4, np.float64)
+        o = np.ascontiguousarray(keyframe_options() if opts is None else opts, KEYFRAME_OPTIONS_DTYPE)
+        res = np.zeros(1, KEYFRAME_RESULT_DTYPE)
+        rc = lib().vx_dmap_create_keyframe_host(c.handle, self._h, C.c_uint64(int(kf_id)), _p(pose),
+                                                None if intr is None else _p(intr), _p(uv), len(uv),
+                                                0 if last_kf_id is None else 1,
+                                                C.c_uint64(0 if last_kf_id is None else int(last_kf_id)), _p(mt),
+                                                len(mt), dptr, int(dt), int(rows), int(cols), int(dstride),
+                                                C.c_uint64(int(first_landmark_id)), _p(o), _p(res))
+        return self._create_done(c, rc, res)
+
+    def create_results(self):
+        """vx_dmap_create_results: the last create_keyframe*'s KEYFRAME_LANDMARK_DTYPE records."""
+        n = C.c_int(0)
+        self.ctx._check(lib().vx_dmap_create_results(self._h, 0, None, C.byref(n)))
+        rec = np.zeros(max(n.value, 1), KEYFRAME_LANDMARK_DTYPE)
+        self.ctx._check(lib().vx_dmap_create_results(self._h, len(rec), _p(rec), C.byref(n)))
+        return rec[:n.value]
+
+    def keyframe_features(self, kf_id):
+        """vx_dmap_keyframe_features: (uv (n, 2), lm_id, flags) of a live keyframe, read from the device."""
+        n = C.c_int(0)
+        self.ctx._check(lib().vx_dmap_keyframe_features(self._h, C.c_uint64(int(kf_id)), 0, None, None, None,
+                                                        C.byref(n)))
+        k = max(n.value, 1)
+        uv, lm, fl = np.zeros((k, 2)), np.zeros(k, np.uint64), np.zeros(k, np.uint8)
+        self.ctx._check(lib().vx_dmap_keyframe_features(self._h, C.c_uint64(int(kf_id)), k, _p(uv), _p(lm), _p(fl),
+                                                        C.byref(n)))
+        return uv[:n.value], lm[:n.value], fl[:n.value]
 
     def cull_results(self):
         """vx_dmap_cull_results: the last cull call's (landmark records, feature records)."""

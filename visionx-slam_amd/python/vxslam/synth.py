@@ -372,6 +372,30 @@ def make_keyframe_pair(seed: int, n: int = 2000, *, width: int = 640, height: in
             "depth": np.ascontiguousarray(depth), "pw_true": pw, "inv": inv}
 
 
+def make_keyframe_scene(seed: int, n: int = 2000, *, depth_hole_frac: float = 0.5, with_depth: bool = True, **pair_kw):
+    """make_keyframe_pair shaped for Tracking::CreateKeyFrame as a whole (tracking.cpp:577-584): the
+    positions of both frames are float-representable (Feature::position comes from cv::KeyPoint::pt),
+    the new keyframe (frame 2) arrives without links (has2 = 0), and the depth pixel of a share
+    `depth_hole_frac` of its features is a hole, so that CreateLandmarksFromDepth leaves features for
+    TriangulateWithLastKeyFrame (with the pair's own depth image only ~4 % of the features reach it).
+    `with_depth=False`: no depth image at all (d["depth"] is None).  Otherwise the dict of
+    make_keyframe_pair."""
+    d = make_keyframe_pair(seed, n, **pair_kw)
+    d["uv1"] = np.ascontiguousarray(d["uv1"].astype(np.float32).astype(np.float64))
+    d["uv2"] = np.ascontiguousarray(d["uv2"].astype(np.float32).astype(np.float64))
+    d["has2"] = np.zeros(n, np.uint8)
+    if not with_depth:
+        d["depth"] = None
+        return d
+    rng = np.random.default_rng(seed ^ 0xD0117)
+    depth = d["depth"]
+    px = (d["uv2"] + 0.5).astype(np.int64)  # the pixel CreateLandmarksFromDepth reads (tracking.cpp:596-597)
+    inside = (px[:, 0] >= 0) & (px[:, 0] < depth.shape[1]) & (px[:, 1] >= 0) & (px[:, 1] < depth.shape[0])
+    hole = inside & (rng.random(n) < depth_hole_frac)
+    depth[px[hole, 1], px[hole, 0]] = 0
+    return d
+
+
 def _pnp_geometry(rng, n, outlier_frac, noise_px, width, height, intr, z_range):
     """World points (float64) seen at pixels uv by a camera at a random T_cw = (q | R, t), pixel noise,
     a fraction `outlier_frac` of the pixels replaced by random ones (flags in `out`)."""
