@@ -30,6 +30,9 @@
  *                                                                core/frontend/tracking.cpp:332-455
  *   vx_essential_ransac   <- cv::findEssentialMat + cv::recoverPose in
  *                            Tracking::EstimatePoseByEssential   core/frontend/tracking.cpp:503-547
+ *   vx_track_essential_*  <- Tracking::TrackLastFrame after Match() (and InitWithSecondFrame's head):
+ *                            distance filter, 2D-2D pairs, findEssentialMat + recoverPose,
+ *                            T_cl * T_lw, ComputeParallax       core/frontend/tracking.cpp:281-330
  *   vx_dmap_*             <- visionx::Map (map.h:13-35) kept resident on the device, updated like
  *                            Map::InsertKeyFrame / InsertLandmark / Landmark::AddObservation
  *   vx_dmap_create_keyframe* <- Tracking::CreateKeyFrame's insertion: CreateLandmarksFromDepth,
@@ -857,6 +860,66 @@ int vx_essential_ransac(vx_ctx* ctx, const float* pts_last, const float* pts_cur
 int vx_essential_ransac_batch(vx_ctx* ctx, int n_problems, const int32_t* offsets, const float* pts_last,
                               const float* pts_curr, const double* intr4, const vx_essential_options* opt,
                               uint8_t* mask, vx_essential_result* out);
+
+/* ---------------------------------------------------------------- TrackLastFrame on the device (track_ess.hip)
+ * <- Tracking::TrackLastFrame after Match(last_frame, curr) (tracking.cpp:281-330) and the same
+ *    sequence at the head of Tracking::InitWithSecondFrame (:207-245): the distance filter (:291-304),
+ *    the cv::Point2f pairs (:509-514), findEssentialMat + recoverPose (:521-528), T_cl * T_lw
+ *    (:539-541) and ComputeParallax (:325, :548-560) as ONE stream-ordered sequence over data that is
+ *    already on the device — the match list and both frames' keypoints — with one synchronisation, in
+ *    the fetch.  No map is involved.
+ *    T_cl * T_lw (Sophus::SE3d): q_cl from R by Shepperd's method (Eigen::Quaterniond(Matrix3d)),
+ *    q = q_cl (x) q_lw (Hamilton product), q *= 2 / (1 + |q|^2) when |q|^2 != 1 (Sophus's first-order
+ *    renormalisation), t = R(q_cl) t_lw + t_cl.  Parity with Sophus itself is unpinned. */
+typedef struct {
+    int32_t min_matches;        /* Tracking::Options::min_matches 50 (tracking.cpp:306) */
+    int32_t min_inliers;        /* Tracking::Options::min_inliers 30 (tracking.cpp:317, :530) */
+    vx_essential_options ess;   /* vx_essential_default_options */
+} vx_track_essential_options;
+
+#define VX_TRACK_ESSENTIAL_FAILED 5 /* !ess.ok || ess.n_inliers < min_inliers (tracking.cpp:317, :523, :530) */
+
+typedef struct {
+    int32_t status;             /* VX_TRACK_OK, VX_TRACK_FEW_MATCHES or VX_TRACK_ESSENTIAL_FAILED */
+    int32_t n_matches, n_good_matches, n_pairs;
+    int32_t n_bad_index;        /* kept matches whose query / train index lies outside the two feature sets
+                                   (skipped, never read; the reference would index out of bounds) */
+    float min_distance;         /* min(100.0f, smallest distance), tracking.cpp:294-297 */
+    double parallax;            /* ComputeParallax(last, curr, kept matches) over the float positions: the sum
+                                   over the kept matches with valid indices / n_good_matches; 0 when FEW_MATCHES */
+    double pose[7];             /* T_cw = T_cl * T_lw (qx qy qz qw tx ty tz); zero when !ess.ok */
+    vx_essential_result ess;    /* as vx_essential_ransac on the pairs (ok = 0 when the call returned early) */
+} vx_track_essential_result;
+
+/* tracking.h:27-28 + tracking.cpp:521: 50 / 30 / vx_essential_default_options */
+void vx_track_essential_default_options(vx_track_essential_options* o);
+/* <- tracking.cpp:291-325, :509-541.  Positions of both frames as vx_track_pnp_async takes the current
+ * frame's: row i = two floats at d_*_xy + i * stride (20 for a slot's vx_keypoint rows, 8 for packed
+ * float2), *d_n_* rows (device).  The match list (query = last frame, train = current frame) as in
+ * vx_track_pnp_async: d_matches == NULL means the result of ctx's last vx_match_slots_async /
+ * vx_match_device_async (VX_ERR_STATE if nothing was matched).  pose_last7 (host): T_lw as qx qy qz qw
+ * tx ty tz, NULL = identity; intr4 (host): fx fy cx cy, non-zero focal lengths;
+ * opt->ess.max_iterations <= 4096.  Enqueued on ctx's stream; no host synchronisation.  Uses buffers
+ * of its own: a vx_track_pnp_* pair, vx_pnp_ransac or vx_essential_ransac may run before the fetch,
+ * and a PnP track and an essential track may be in flight together. */
+int vx_track_essential_async(vx_ctx* ctx, const float* d_last_xy, int64_t last_stride_bytes, const int32_t* d_n_last,
+                             const float* d_curr_xy, int64_t curr_stride_bytes, const int32_t* d_n_curr,
+                             const vx_match* d_matches, const int32_t* d_n_matches, int cap_matches,
+                             const double* pose_last7, const double* intr4, const vx_track_essential_options* opt);
+/* Host-input form (what visionx::EssentialTracker calls): both frames' descriptor rows (32 B each) and
+ * float2 positions are staged and uploaded in ONE copy, matched on the device (query = last frame,
+ * `ratio`) and fed straight into vx_track_essential_async.  May block at its start until the PREVIOUS
+ * call's upload has left the pinned staging block it reuses, as vx_track_pnp_host_async. */
+int vx_track_essential_host_async(vx_ctx* ctx, const uint8_t* last_desc, int n_last, const float* last_xy,
+                                  const uint8_t* curr_desc, int n_curr, const float* curr_xy, float ratio,
+                                  const double* pose_last7, const double* intr4,
+                                  const vx_track_essential_options* opt);
+/* One device-to-host copy (result | pair_match | mask) and one synchronisation; `status` is then set
+ * in the order of tracking.cpp:306, :317.  pair_match[k] = index in the match list of pair k
+ * (ascending), mask[k] = recoverPose's output mask of pair k; either may be NULL.  VX_ERR_CAPACITY
+ * (with *out filled) if an array is given and n_pairs > cap_pairs. */
+int vx_track_essential_fetch(vx_ctx* ctx, vx_track_essential_result* out, int32_t* pair_match, uint8_t* mask,
+                             int cap_pairs);
 
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,

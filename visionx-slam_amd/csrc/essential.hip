@@ -969,6 +969,41 @@ __global__ void __launch_bounds__(kThreads * 4) k_em_final(EmArgs a, const EmSta
 size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
+
+int ess_enqueue(vx_ctx* c, int P, int hmax, int n_bound, const EmDeviceArgs& d, DevBuf& hyp) {
+    hmax = std::max(hmax, 1);
+    const size_t rec_bytes = align16((size_t)P * hmax * sizeof(EmRec));
+    VX_HIP(c, hyp.ensure(rec_bytes + (size_t)P * (sizeof(EmState) + sizeof(int))));
+    EmArgs a{};
+    a.offsets = d.offsets;
+    a.intr = d.intr;
+    a.opt = d.opt;
+    a.p1 = d.p1;
+    a.p2 = d.p2;
+    a.rec = hyp.as<EmRec>();
+    a.hmax = hmax;
+    a.out = d.out;
+    a.mask = d.mask;
+    int* gate = reinterpret_cast<int*>(hyp.as<uint8_t>() + rec_bytes + (size_t)P * sizeof(EmState));
+    // everything at once while the whole hypothesis grid is resident at the same time (8 one-wave
+    // workgroups per CU at this kernel's register count); beyond that, gate by the remaining budget
+    if (!c->n_cus) c->n_cus = std::max(vx_device_cus(c->device), 1);
+    const int first = (int64_t)P * hmax <= 8 * (int64_t)c->n_cus ? hmax : std::min(hmax, kFirstChunk);
+    VX_HIP(c, launch(c, kStEmHyp, k_em_hyp, dim3(first, P), dim3(kThreads), 0, c->stream, a, 0, (const int*)nullptr));
+    if (hmax > first) {
+        VX_HIP(c, launch(c, kStEmSelect, k_em_gate, dim3(P), dim3(64), 0, c->stream, a, gate));
+        VX_HIP(c, launch(c, kStEmHyp, k_em_hyp, dim3(hmax - first, P), dim3(kThreads), 0, c->stream, a, first,
+                         (const int*)gate));
+    }
+    EmState* st = reinterpret_cast<EmState*>(hyp.as<uint8_t>() + rec_bytes);
+    // the per-match grids are sized by the host-side bound; the kernels take n from the device offsets
+    const dim3 pgrid((std::max(n_bound, 1) + 4 * kThreads - 1) / (4 * kThreads), P);
+    VX_HIP(c, launch(c, kStEmSelect, k_em_pick, dim3(P), dim3(64), 0, c->stream, a, st));
+    VX_HIP(c, launch(c, kStEmSelect, k_em_cheir, pgrid, dim3(4 * kThreads), 0, c->stream, a, (const EmState*)st));
+    VX_HIP(c, launch(c, kStEmSelect, k_em_final, pgrid, dim3(4 * kThreads), 0, c->stream, a, (const EmState*)st));
+    return VX_OK;
+}
+
 }  // namespace vx
 
 using namespace vx;
@@ -1027,39 +1062,21 @@ int vx_essential_ransac_batch(vx_ctx* c, int P, const int32_t* offsets, const fl
     }
     VX_HIP(c, c->rs_in.ensure(in_bytes));
     VX_HIP(c, hipMemcpyAsync(c->rs_in.p, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    const size_t rec_bytes = align16((size_t)P * hmax * sizeof(EmRec));
-    VX_HIP(c, c->rs_hyp.ensure(rec_bytes + (size_t)P * (sizeof(EmState) + sizeof(int))));
-    int nmax = 1;
-    for (int p = 0; p < P; ++p) nmax = std::max(nmax, offsets[p + 1] - offsets[p]);
     const size_t out_bytes = align16((size_t)P * sizeof(vx_essential_result)) + (size_t)std::max<int64_t>(N, 1);
     VX_HIP(c, c->rs_out.ensure(out_bytes));
     uint8_t* din = c->rs_in.as<uint8_t>();
-    EmArgs a{};
-    a.offsets = reinterpret_cast<const int*>(din + o_off);
-    a.intr = reinterpret_cast<const double*>(din + o_intr);
-    a.opt = reinterpret_cast<const vx_essential_options*>(din + o_opt);
-    a.p1 = reinterpret_cast<const float*>(din + o_p1);
-    a.p2 = reinterpret_cast<const float*>(din + o_p2);
-    a.rec = c->rs_hyp.as<EmRec>();
-    a.hmax = hmax;
-    a.out = c->rs_out.as<vx_essential_result>();
-    a.mask = c->rs_out.as<uint8_t>() + align16((size_t)P * sizeof(vx_essential_result));
-    int* gate = reinterpret_cast<int*>(c->rs_hyp.as<uint8_t>() + rec_bytes + (size_t)P * sizeof(EmState));
-    // everything at once while the whole hypothesis grid is resident at the same time (8 one-wave
-    // workgroups per CU at this kernel's register count); beyond that, gate by the remaining budget
-    if (!c->n_cus) c->n_cus = std::max(vx_device_cus(c->device), 1);
-    const int first = (int64_t)P * hmax <= 8 * (int64_t)c->n_cus ? hmax : std::min(hmax, kFirstChunk);
-    VX_HIP(c, launch(c, kStEmHyp, k_em_hyp, dim3(first, P), dim3(kThreads), 0, c->stream, a, 0, (const int*)nullptr));
-    if (hmax > first) {
-        VX_HIP(c, launch(c, kStEmSelect, k_em_gate, dim3(P), dim3(64), 0, c->stream, a, gate));
-        VX_HIP(c, launch(c, kStEmHyp, k_em_hyp, dim3(hmax - first, P), dim3(kThreads), 0, c->stream, a, first,
-                         (const int*)gate));
-    }
-    EmState* st = reinterpret_cast<EmState*>(c->rs_hyp.as<uint8_t>() + rec_bytes);
-    const dim3 pgrid((nmax + 4 * kThreads - 1) / (4 * kThreads), P);
-    VX_HIP(c, launch(c, kStEmSelect, k_em_pick, dim3(P), dim3(64), 0, c->stream, a, st));
-    VX_HIP(c, launch(c, kStEmSelect, k_em_cheir, pgrid, dim3(4 * kThreads), 0, c->stream, a, (const EmState*)st));
-    VX_HIP(c, launch(c, kStEmSelect, k_em_final, pgrid, dim3(4 * kThreads), 0, c->stream, a, (const EmState*)st));
+    EmDeviceArgs d{};
+    d.offsets = reinterpret_cast<const int*>(din + o_off);
+    d.intr = reinterpret_cast<const double*>(din + o_intr);
+    d.opt = reinterpret_cast<const vx_essential_options*>(din + o_opt);
+    d.p1 = reinterpret_cast<const float*>(din + o_p1);
+    d.p2 = reinterpret_cast<const float*>(din + o_p2);
+    d.out = c->rs_out.as<vx_essential_result>();
+    d.mask = c->rs_out.as<uint8_t>() + align16((size_t)P * sizeof(vx_essential_result));
+    int nmax = 1;
+    for (int p = 0; p < P; ++p) nmax = std::max(nmax, offsets[p + 1] - offsets[p]);
+    int rc;
+    if ((rc = ess_enqueue(c, P, hmax, nmax, d, c->rs_hyp))) return rc;
     VX_HIP(c, c->rs_host_out.ensure(out_bytes));
     VX_HIP(c, hipMemcpyAsync(c->rs_host_out.p, c->rs_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     VX_HIP(c, hipStreamSynchronize(c->stream));

@@ -47,12 +47,14 @@
 #include "vx_internal.hpp"
 #include "dmap.hpp"
 #include "lm_hash.hpp"
+#include "track_common.hpp"
 
 namespace vx {
 namespace {
 
-constexpr int kBlock = 1024;
-constexpr int kWaves = kBlock / 64;
+using trk::block_rank;
+using trk::kBlock;
+using trk::kWaves;
 
 struct TrackArgs {
     // match list (query = last keyframe feature, train = current frame feature)
@@ -91,26 +93,6 @@ struct TrackArgs {
     vx_pnp_options* opt_out;
 };
 
-// Exclusive rank of this thread's flag among the block's flags (thread order) and their total.
-// Two barriers: the wave counts are read by everyone before the next call rewrites them.
-__device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t b = __ballot(flag);
-    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-    if (lane == 0) s_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const int v = s_cnt[w];
-        before += w < wave ? v : 0;
-        all += v;
-    }
-    __syncthreads();
-    *total = all;
-    return before + in_wave;
-}
-
 __device__ __forceinline__ void curr_pos(const TrackArgs& a, int i, float* x, float* y) {
     const float* p = reinterpret_cast<const float*>(a.curr_xy + (int64_t)i * a.stride);
     *x = p[0];
@@ -125,37 +107,9 @@ __global__ void __launch_bounds__(kBlock) k_track_pairs(TrackArgs a) {
     const int n = min(max(*a.n_matches, 0), a.cap_matches);
     const int n_curr = *a.n_curr;
 
-    // 1: min distance (tracking.cpp:345-348)
-    float mn = 100.0f;
-    for (int i = tid; i < n; i += kBlock) {
-        const float d = a.matches[i].distance;
-        if (d < mn) mn = d;
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(mn, off);
-        if (o < mn) mn = o;
-    }
-    if (lane == 0) s_min[wave] = mn;
-    __syncthreads();
-    mn = s_min[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w)
-        if (s_min[w] < mn) mn = s_min[w];
-    // 2: std::max(2 * min_dist, 30.0f) (:350)
-    const float thr = fmaxf(2 * mn, 30.0f);
-
-    // 3: the kept matches, in match order
-    int n_good = 0;
-    for (int base = 0; base < n; base += kBlock) {
-        const int i = base + tid;
-        const bool keep = i < n && a.matches[i].distance <= thr;
-        int total;
-        const int r = block_rank(keep, s_cnt, &total);
-        if (keep) a.good[n_good + r] = i;
-        n_good += total;
-    }
-    __syncthreads();  // a.good is read by other threads below (one workgroup: one CU, one L1)
+    // 1-3: min distance, threshold, the kept matches in match order (track_common.hpp)
+    float mn;
+    const int n_good = trk::filter_matches(a.matches, n, a.good, s_cnt, s_min, &mn);
 
     // 4 + 5: pairs in kept-match order, parallax partials
     const bool enough = n_good >= a.min_matches;

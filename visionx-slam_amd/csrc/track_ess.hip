@@ -1,0 +1,407 @@
+// track_ess.hip — Tracking::TrackLastFrame (core/frontend/tracking.cpp:281-330) and the head of
+// Tracking::InitWithSecondFrame (:207-245) from the match list to the composed pose without leaving
+// the device (vx_track_essential_async / vx_track_essential_fetch).
+//
+// The reference filters the matches by distance (:291-304), builds the cv::Point2f pairs (:509-514),
+// calls findEssentialMat + recoverPose on them (:521-528), composes T_cl * T_lw (:539-541) and
+// averages the pixel displacement of the kept matches (ComputeParallax, :325, :548-560).  Everything
+// those steps read is already resident: the match list (match.hip) and both frames' keypoints
+// (extraction slots, or any float2 rows).  The sequence is
+//
+//   k_track_epairs (1 workgroup) -> k_em_hyp .. k_em_final [ess_enqueue] -> k_track_epose (1 lane)
+//
+// with no host step between and one synchronisation, in the fetch.
+//
+// k_track_epairs is ONE workgroup for the reason k_track_pairs is (track.hip): the pairs keep the
+// match order, which fixes RANSAC's sample stream, so the compaction is one block-wide ordered scan.
+// Its stages 1-3 (min distance, threshold, kept list) ARE k_track_pairs' (track_common.hpp); then
+//   4  pair gather   kept match j (in order): index bounds against the device counts (a match out of
+//                    range is counted and never dereferenced); survivors compacted by ballot + mbcnt,
+//                    16 wave totals in LDS and a running base into pts_last / pts_curr (the floats
+//                    as they are) and pair_match
+//   5  parallax      sqrt(dx * dx + dy * dy) on the widened doubles; per-thread partial, wave
+//                    butterfly, wave partials summed in wave order: a fixed order
+//   6  record        offsets {0, n_pairs} (or {0, 0} when the min_matches gate of :306 fails: the
+//                    essential kernels then return ok = 0 without a hypothesis), intrinsics, options
+// No atomics decide a position; no scratch.
+//
+// k_track_epose: one lane restates Sophus::SE3d(R, t) * T_lw after k_em_final — Shepperd's branches
+// as PoseFromRt (host/src/geometry.cpp), the Hamilton product, the first-order renormalisation,
+// t = R(q_cl) t_lw + t_cl in SE3d::operator*(Vec3d)'s operation order (host/include/visionx/types.h)
+// — so the host adapters, tests/track_ess_ref.py and this kernel run the same IEEE sequence.
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+
+#include "vx_internal.hpp"
+#include "track_common.hpp"
+
+namespace vx {
+namespace {
+
+using trk::block_rank;
+using trk::kBlock;
+using trk::kWaves;
+
+struct EPairArgs {
+    // match list (query = last frame feature, train = current frame feature)
+    const vx_match* matches;
+    const int* n_matches;
+    int cap_matches;
+    // positions: two floats at *_xy + i * stride, *n_* rows
+    const uint8_t* last_xy;
+    int64_t last_stride;
+    const int* n_last;
+    const uint8_t* curr_xy;
+    int64_t curr_stride;
+    const int* n_curr;
+    // options
+    int min_matches;
+    vx_essential_options ess;
+    double intr[4];
+    // scratch + outputs
+    int* good;              // cap_matches: kept match indices, match order
+    float* p1;              // 2 per pair (pts_last)
+    float* p2;              // 2 per pair (pts_curr)
+    int* pair_match;        // per pair
+    uint8_t* mask;          // per pair (zeroed here, written by k_em_cheir / k_em_final)
+    vx_track_essential_result* res;
+    int* offsets;           // 2
+    double* intr_out;       // 4
+    vx_essential_options* opt_out;
+};
+
+__global__ void __launch_bounds__(kBlock) k_track_epairs(EPairArgs a) {
+    __shared__ int s_cnt[kWaves];
+    __shared__ float s_min[kWaves];
+    __shared__ double s_sum[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(max(*a.n_matches, 0), a.cap_matches);
+    const int n_last = *a.n_last, n_curr = *a.n_curr;
+
+    // 1-3: min distance, threshold, the kept matches in match order (track_common.hpp)
+    float mn;
+    const int n_good = trk::filter_matches(a.matches, n, a.good, s_cnt, s_min, &mn);
+
+    // 4 + 5: pairs in kept-match order, parallax partials
+    const bool enough = n_good >= a.min_matches;
+    int n_pairs = 0, n_bad = 0;
+    double part = 0.0;
+    for (int base = 0; base < n_good; base += kBlock) {
+        const int j = base + tid;
+        bool pair = false, bad_index = false;
+        int mi = 0;
+        float lx = 0.f, ly = 0.f, cx = 0.f, cy = 0.f;
+        if (j < n_good) {
+            mi = a.good[j];
+            const vx_match m = a.matches[mi];
+            if (m.query_idx < 0 || m.query_idx >= n_last || m.train_idx < 0 || m.train_idx >= n_curr) {
+                bad_index = true;
+            } else {
+                const float* pl = reinterpret_cast<const float*>(a.last_xy + (int64_t)m.query_idx * a.last_stride);
+                const float* pc = reinterpret_cast<const float*>(a.curr_xy + (int64_t)m.train_idx * a.curr_stride);
+                lx = pl[0];
+                ly = pl[1];
+                cx = pc[0];
+                cy = pc[1];
+                pair = true;
+                if (enough) {  // ComputeParallax (:548-560): (p1 - p2).norm() in double
+                    const double dx = (double)lx - (double)cx;
+                    const double dy = (double)ly - (double)cy;
+                    part += sqrt(dx * dx + dy * dy);
+                }
+            }
+        }
+        int total;
+        const int r = block_rank(pair, s_cnt, &total);
+        if (pair) {
+            const int k = n_pairs + r;
+            a.p1[2 * k] = lx;
+            a.p1[2 * k + 1] = ly;
+            a.p2[2 * k] = cx;
+            a.p2[2 * k + 1] = cy;
+            a.pair_match[k] = mi;
+            a.mask[k] = 0;
+        }
+        n_pairs += total;
+        n_bad += bad_index ? 1 : 0;
+    }
+
+    // 5: parallax (and the skipped-index count), fixed order
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        part += __shfl_xor(part, off);
+        n_bad += __shfl_xor(n_bad, off);
+    }
+    if (lane == 0) {
+        s_sum[wave] = part;
+        s_cnt[wave] = n_bad;
+    }
+    __syncthreads();
+
+    // 6: result counts and the essential problem record
+    if (tid == 0) {
+        double sum = s_sum[0];
+        n_bad = s_cnt[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) {
+            sum += s_sum[w];
+            n_bad += s_cnt[w];
+        }
+        vx_track_essential_result* r = a.res;
+        r->status = 0;
+        r->n_matches = n;
+        r->n_good_matches = n_good;
+        r->n_pairs = n_pairs;
+        r->n_bad_index = n_bad;
+        r->min_distance = mn;
+        r->parallax = enough && n_good > 0 ? sum / (double)n_good : 0.0;  // cnt > 0 ? sum / cnt : 0 (:559)
+        a.offsets[0] = 0;
+        a.offsets[1] = enough ? n_pairs : 0;  // (:306)
+        for (int k = 0; k < 4; ++k) a.intr_out[k] = a.intr[k];
+        *a.opt_out = a.ess;
+    }
+}
+
+struct EPoseArgs {
+    vx_track_essential_result* res;
+    double pose_last[7];  // T_lw: qx qy qz qw tx ty tz
+};
+
+// Sophus::SE3d(R, t) * T_lw by one lane (tracking.cpp:539-541); zero when recoverPose gave nothing
+__global__ void __launch_bounds__(64) k_track_epose(EPoseArgs a) {
+    if (threadIdx.x != 0) return;
+    const vx_essential_result* e = &a.res->ess;
+    double out[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (e->ok) {
+        double R[9];
+        for (int k = 0; k < 9; ++k) R[k] = e->R[k];
+        // q_cl: Shepperd's method, as PoseFromRt (Eigen::Quaterniond(Matrix3d))
+        double x, y, z, w;
+        const double tr = R[0] + R[4] + R[8];
+        if (tr > 0.0) {
+            const double s = sqrt(tr + 1.0) * 2.0;
+            w = 0.25 * s; x = (R[7] - R[5]) / s; y = (R[2] - R[6]) / s; z = (R[3] - R[1]) / s;
+        } else if (R[0] > R[4] && R[0] > R[8]) {
+            const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
+            w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s;
+        } else if (R[4] > R[8]) {
+            const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
+            w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s;
+        } else {
+            const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
+            w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s;
+        }
+        const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
+        const double ax = x * inv, ay = y * inv, az = z * inv, aw = w * inv;
+        const double bx = a.pose_last[0], by = a.pose_last[1], bz = a.pose_last[2], bw = a.pose_last[3];
+        // q = q_cl (x) q_lw, Eigen's coefficient order
+        double qw = aw * bw - ax * bx - ay * by - az * bz;
+        double qx = aw * bx + ax * bw + ay * bz - az * by;
+        double qy = aw * by + ay * bw + az * bx - ax * bz;
+        double qz = aw * bz + az * bw + ax * by - ay * bx;
+        // Sophus's first-order renormalisation
+        const double n2 = qx * qx + qy * qy + qz * qz + qw * qw;
+        if (n2 != 1.0) {
+            const double sc = 2.0 / (1.0 + n2);
+            qx *= sc; qy *= sc; qz *= sc; qw *= sc;
+        }
+        // t = T_cl * t_lw (SE3d::operator*(Vec3d))
+        const double px = a.pose_last[4], py = a.pose_last[5], pz = a.pose_last[6];
+        const double ux = ay * pz - az * py, uy = az * px - ax * pz, uz = ax * py - ay * px;
+        const double wx = 2 * ux, wy = 2 * uy, wz = 2 * uz;
+        out[0] = qx; out[1] = qy; out[2] = qz; out[3] = qw;
+        out[4] = px + aw * wx + (ay * wz - az * wy) + e->t[0];
+        out[5] = py + aw * wy + (az * wx - ax * wz) + e->t[1];
+        out[6] = pz + aw * wz + (ax * wy - ay * wx) + e->t[2];
+    }
+    for (int k = 0; k < 7; ++k) a.res->pose[k] = out[k];
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// packed result block: vx_track_essential_result | pair_match[cap] | mask[cap]
+size_t off_pair_match() { return align16(sizeof(vx_track_essential_result)); }
+size_t off_mask(int cap) { return off_pair_match() + align16((size_t)cap * sizeof(int32_t)); }
+size_t packed_bytes(int cap) { return off_mask(cap) + align16((size_t)cap); }
+
+bool stride_ok(int64_t s) { return s >= 8 && !(s & 3); }
+
+// the checks on the host values both entry points make before anything touches a device
+int check_host_args(vx_ctx* c, const double* intr4, const vx_track_essential_options* opt) {
+    if (!intr4 || !opt) return set_error(c, VX_ERR_INVALID, "vx_track_essential: null intrinsics / options");
+    if (!(intr4[0] != 0.0 && intr4[1] != 0.0 && intr4[0] + intr4[1] != 0.0))
+        return set_error(c, VX_ERR_INVALID, "zero focal length");
+    if (opt->ess.max_iterations > 4096)
+        return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", opt->ess.max_iterations);
+    if (!(opt->ess.threshold >= 0.0)) return set_error(c, VX_ERR_INVALID, "bad essential options");
+    return VX_OK;
+}
+
+}  // namespace
+}  // namespace vx
+
+using namespace vx;
+
+extern "C" {
+
+void vx_track_essential_default_options(vx_track_essential_options* o) {
+    if (!o) return;
+    o->min_matches = 50;  // Tracking::Options (tracking.h:27-28)
+    o->min_inliers = 30;
+    vx_essential_default_options(&o->ess);
+}
+
+int vx_track_essential_async(vx_ctx* c, const float* d_last_xy, int64_t last_stride_bytes, const int32_t* d_n_last,
+                             const float* d_curr_xy, int64_t curr_stride_bytes, const int32_t* d_n_curr,
+                             const vx_match* d_matches, const int32_t* d_n_matches, int cap_matches,
+                             const double* pose_last7, const double* intr4, const vx_track_essential_options* opt) {
+    if (!c) return VX_ERR_INVALID;
+    if (!d_last_xy || !d_n_last || !d_curr_xy || !d_n_curr)
+        return set_error(c, VX_ERR_INVALID, "vx_track_essential_async: null argument");
+    int rc;
+    if ((rc = check_host_args(c, intr4, opt))) return rc;
+    if (!stride_ok(last_stride_bytes) || !stride_ok(curr_stride_bytes))
+        return set_error(c, VX_ERR_INVALID, "position strides %lld / %lld: multiples of 4, at least 8",
+                         (long long)last_stride_bytes, (long long)curr_stride_bytes);
+    if (d_matches) {
+        if (!d_n_matches || cap_matches < 0) return set_error(c, VX_ERR_INVALID, "match list without a count / capacity");
+    } else {
+        if (!c->match_valid) return set_error(c, VX_ERR_STATE, "no match enqueued on this context");
+        d_matches = c->matches.as<vx_match>();
+        d_n_matches = c->match_count.as<int32_t>();
+        cap_matches = c->match_cap;
+    }
+    VX_HIP(c, hipSetDevice(c->device));
+
+    const int cap = std::max(cap_matches, 1);
+    VX_HIP(c, c->te_good.ensure((size_t)cap * sizeof(int)));
+    VX_HIP(c, c->te_p1.ensure((size_t)cap * 2 * sizeof(float)));
+    VX_HIP(c, c->te_p2.ensure((size_t)cap * 2 * sizeof(float)));
+    VX_HIP(c, c->te_prob.ensure(16 + 4 * sizeof(double) + sizeof(vx_essential_options)));
+    VX_HIP(c, c->te_out.ensure(packed_bytes(cap)));
+    uint8_t* prob = c->te_prob.as<uint8_t>();
+    uint8_t* out = c->te_out.as<uint8_t>();
+    EPairArgs a{};
+    a.matches = d_matches;
+    a.n_matches = d_n_matches;
+    a.cap_matches = cap_matches;
+    a.last_xy = reinterpret_cast<const uint8_t*>(d_last_xy);
+    a.last_stride = last_stride_bytes;
+    a.n_last = d_n_last;
+    a.curr_xy = reinterpret_cast<const uint8_t*>(d_curr_xy);
+    a.curr_stride = curr_stride_bytes;
+    a.n_curr = d_n_curr;
+    a.min_matches = opt->min_matches;
+    a.ess = opt->ess;
+    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+    a.good = c->te_good.as<int>();
+    a.p1 = c->te_p1.as<float>();
+    a.p2 = c->te_p2.as<float>();
+    a.pair_match = reinterpret_cast<int*>(out + off_pair_match());
+    a.mask = out + off_mask(cap);
+    a.res = reinterpret_cast<vx_track_essential_result*>(out);
+    a.offsets = reinterpret_cast<int*>(prob);
+    a.intr_out = reinterpret_cast<double*>(prob + 16);
+    a.opt_out = reinterpret_cast<vx_essential_options*>(prob + 16 + 4 * sizeof(double));
+    c->te_valid = false;
+    VX_HIP(c, launch(c, kStTrackEPairs, k_track_epairs, dim3(1), dim3(kBlock), 0, c->stream, a));
+    EmDeviceArgs d{};
+    d.offsets = a.offsets;
+    d.intr = a.intr_out;
+    d.opt = a.opt_out;
+    d.p1 = a.p1;
+    d.p2 = a.p2;
+    d.out = &a.res->ess;
+    d.mask = a.mask;
+    // the per-match grids are sized by the capacity: the pair count is known on the device only
+    if ((rc = ess_enqueue(c, 1, std::max(1, opt->ess.max_iterations), cap, d, c->te_hyp))) return rc;
+    EPoseArgs p{};
+    p.res = a.res;
+    p.pose_last[3] = 1.0;
+    if (pose_last7)
+        for (int i = 0; i < 7; ++i) p.pose_last[i] = pose_last7[i];
+    VX_HIP(c, launch(c, kStTrackEPose, k_track_epose, dim3(1), dim3(64), 0, c->stream, p));
+    c->te_cap = cap;
+    c->te_min_matches = opt->min_matches;
+    c->te_min_inliers = opt->min_inliers;
+    c->te_valid = true;
+    return VX_OK;
+}
+
+int vx_track_essential_host_async(vx_ctx* c, const uint8_t* last_desc, int n_last, const float* last_xy,
+                                  const uint8_t* curr_desc, int n_curr, const float* curr_xy, float ratio,
+                                  const double* pose_last7, const double* intr4,
+                                  const vx_track_essential_options* opt) {
+    if (!c) return VX_ERR_INVALID;
+    if (n_last < 0 || n_curr < 0 || (n_last && (!last_desc || !last_xy)) || (n_curr && (!curr_desc || !curr_xy)))
+        return set_error(c, VX_ERR_INVALID, "vx_track_essential_host_async: bad descriptor / position arguments");
+    int rc;
+    if ((rc = check_host_args(c, intr4, opt))) return rc;
+    VX_HIP(c, hipSetDevice(c->device));
+    // one staged block: {n_last, n_curr} | last rows | current rows | last positions | current positions.
+    // The row capacities are rounded up to 256 as in vx_track_pnp_host_async (one launch configuration,
+    // and one captured match graph, for frames with about as many features).
+    const int cap_q = (std::max(n_last, 1) + 255) & ~255, cap_t = (std::max(n_curr, 1) + 255) & ~255;
+    const size_t o_q = 16, o_t = o_q + (size_t)cap_q * 32, o_qxy = o_t + (size_t)cap_t * 32,
+                 o_txy = o_qxy + (size_t)cap_q * 8, bytes = o_txy + (size_t)cap_t * 8;
+    // (the one place this entry can block: until the previous call's upload has left the staging)
+    if (c->te_in_event) VX_HIP(c, hipEventSynchronize(c->te_in_event));
+    else VX_HIP(c, hipEventCreateWithFlags(&c->te_in_event, hipEventDisableTiming));
+    VX_HIP(c, c->te_in_host.ensure(bytes));
+    VX_HIP(c, c->te_in.ensure(bytes));
+    uint8_t* h = static_cast<uint8_t*>(c->te_in_host.p);
+    const int32_t counts[4] = {n_last, n_curr, 0, 0};
+    std::memcpy(h, counts, sizeof counts);
+    // rows between the counts and the rounded capacities are not filled: every kernel stops at the
+    // device-side counts, so what the upload carries there is never read
+    if (n_last) {
+        std::memcpy(h + o_q, last_desc, (size_t)n_last * 32);
+        std::memcpy(h + o_qxy, last_xy, (size_t)n_last * 8);
+    }
+    if (n_curr) {
+        std::memcpy(h + o_t, curr_desc, (size_t)n_curr * 32);
+        std::memcpy(h + o_txy, curr_xy, (size_t)n_curr * 8);
+    }
+    VX_HIP(c, hipMemcpyAsync(c->te_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
+    VX_HIP(c, hipEventRecord(c->te_in_event, c->stream));
+    const uint8_t* d = c->te_in.as<uint8_t>();
+    const int32_t* dn = c->te_in.as<int32_t>();
+    if ((rc = vx_match_device_async(c, d + o_q, dn, cap_q, d + o_t, dn + 1, cap_t, ratio))) return rc;
+    // the list just enqueued, named explicitly with the capacity it was enqueued with
+    return vx_track_essential_async(c, reinterpret_cast<const float*>(d + o_qxy), 8, dn,
+                                    reinterpret_cast<const float*>(d + o_txy), 8, dn + 1, c->matches.as<vx_match>(),
+                                    c->match_count.as<int32_t>(), cap_q, pose_last7, intr4, opt);
+}
+
+int vx_track_essential_fetch(vx_ctx* c, vx_track_essential_result* out, int32_t* pair_match, uint8_t* mask,
+                             int cap_pairs) {
+    if (!c || !out) return c ? set_error(c, VX_ERR_INVALID, "vx_track_essential_fetch: null result") : VX_ERR_INVALID;
+    if (!c->te_valid) return set_error(c, VX_ERR_STATE, "no vx_track_essential_async enqueued");
+    VX_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = packed_bytes(c->te_cap);
+    VX_HIP(c, c->te_host.ensure(bytes));
+    VX_HIP(c, hipMemcpyAsync(c->te_host.p, c->te_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) prof_collect(c);
+    const uint8_t* h = static_cast<const uint8_t*>(c->te_host.p);
+    std::memcpy(out, h, sizeof *out);
+    if (out->n_good_matches < c->te_min_matches) out->status = VX_TRACK_FEW_MATCHES;                       // (:306)
+    else if (!out->ess.ok || out->ess.n_inliers < c->te_min_inliers) out->status = VX_TRACK_ESSENTIAL_FAILED;  // (:317)
+    else out->status = VX_TRACK_OK;
+    const int np = out->n_pairs;
+    if ((pair_match || mask) && np > cap_pairs)
+        return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
+    if (pair_match && np) std::memcpy(pair_match, h + off_pair_match(), (size_t)np * sizeof(int32_t));
+    if (mask && np) std::memcpy(mask, h + off_mask(c->te_cap), (size_t)np);
+    return VX_OK;
+}
+
+}  // extern "C"
+
+static_assert(sizeof(vx_track_essential_options) == 48, "vx_track_essential_options layout (python TRACK_ESS_OPTIONS_DTYPE)");
+static_assert(sizeof(vx_track_essential_result) == 288, "vx_track_essential_result layout (python TRACK_ESS_RESULT_DTYPE)");
+static_assert(offsetof(vx_track_essential_result, parallax) == 24 && offsetof(vx_track_essential_result, pose) == 32 &&
+                  offsetof(vx_track_essential_result, ess) == 88,
+              "vx_track_essential_result has no implicit padding");

@@ -70,6 +70,8 @@ enum Stage : int {
     kStKfFeat,        // CreateKeyFrame on the resident map: feature rows + depth (k_kf_feat)
     kStKfMatch,       // its triangulation gate per match (k_kf_match)
     kStKfCommit,      // its ordered compactions and the map edit (k_kf_commit)
+    kStTrackEPairs,   // TrackLastFrame's filter + 2D-2D pair gather (k_track_epairs)
+    kStTrackEPose,    // its T_cl * T_lw (k_track_epose)
     kStCount
 };
 
@@ -236,6 +238,17 @@ struct vx_ctx {
     int tk_min_matches = 0, tk_min_inliers = 0;
     bool tk_valid = false;
 
+    // ---- TrackLastFrame on the device (track_ess.hip): buffers of its own again, so a PnP track, an
+    // essential track and the RANSAC entry points may all be in flight together
+    vx::DevBuf te_good, te_p1, te_p2, te_prob, te_hyp, te_out;  // kept-match list, pairs, essential record, packed result
+    vx::PinnedBuf te_host;
+    vx::PinnedBuf te_in_host;    // vx_track_essential_host_async: descriptors + positions staged for one upload ...
+    vx::DevBuf te_in;            // ... into one device block
+    hipEvent_t te_in_event = nullptr;  // (recorded after that upload)
+    int te_cap = 0;              // match capacity of the enqueued call (sizes the packed result)
+    int te_min_matches = 0, te_min_inliers = 0;
+    bool te_valid = false;
+
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {
         vx::DevBuf wptr, wlm, wfl, cam, wid, wuv, lid, bad, optr, okf, ofi, pos, hkey, hval, f_lm, f_pv, f_first,
@@ -329,6 +342,24 @@ struct PnpDeviceArgs {
     uint8_t* mask;                // per correspondence
 };
 int pnp_enqueue(vx_ctx* c, int P, int hmax, const PnpDeviceArgs& d, DevBuf& hyp);
+
+// Essential-matrix RANSAC + recoverPose on problems already in device memory (essential.hip), the
+// counterpart of pnp_enqueue: k_em_hyp over (hmax, P) (in two launches with k_em_gate between when
+// the grid exceeds what is resident at once), k_em_pick over P, k_em_cheir and k_em_final over
+// (n_bound / 256, P), enqueued on c->stream, nothing synchronised.  Problem p owns matches
+// [offsets[p], offsets[p + 1]) — read on the device; n_bound is the host-side bound of the largest
+// problem that sizes the per-match grids — and runs min(opt[p].max_iterations, 4096, hmax) hypotheses.
+// `hyp` is the hypothesis scratch.  vx_essential_ransac_batch and vx_track_essential_async both end here.
+struct EmDeviceArgs {
+    const int* offsets;                // P + 1
+    const double* intr;                // 4 per problem
+    const vx_essential_options* opt;   // per problem
+    const float* p1;                   // 2 per match (pts_last)
+    const float* p2;                   // 2 per match (pts_curr)
+    vx_essential_result* out;          // per problem
+    uint8_t* mask;                     // per match
+};
+int ess_enqueue(vx_ctx* c, int P, int hmax, int n_bound, const EmDeviceArgs& d, DevBuf& hyp);
 
 // Runs `enqueue` (which only enqueues work on c->stream) through the context's graph cache: the
 // first call with a key runs eagerly (so every buffer it needs gets allocated outside a capture),

@@ -52,4 +52,81 @@ private:
     std::vector<float> xy_;
 };
 
+// Tracking::TrackLastFrame (core/frontend/tracking.cpp:281-330) and the head of
+// Tracking::InitWithSecondFrame (:207-245) as one device-resident sequence
+// (vx_track_essential_host_async + vx_track_essential_fetch, csrc/track_ess.hip):
+//
+//   matcher_->Match(last_frame_, current_frame_, matches)           (:289)
+//   distance filter, min_matches gate                               (:291-310)
+//   cv::Point2f pairs, findEssentialMat + recoverPose               (:509-528)
+//   min_inliers gate                                                (:317, :530)
+//   curr->SetPose(Sophus::SE3d(R, t) * last->Pose())                (:539-541)
+//   last_inliers_, last_parallax_ = ComputeParallax(...)            (:324-325)
+//
+// with one upload (both descriptor sets + both position sets) and one synchronisation.  No map is read.
+class EssentialTracker {
+public:
+    struct Options {                     // Tracking::Options (tracking.h:27-28), ORBMatcher::Options
+        int min_matches = 50;
+        int min_inliers = 30;
+        float nn_ratio = 0.8f;           // orb_matcher.h:12
+    };
+    // ctx: the context the calls are queued on (not owned); nullptr = the calling thread's own
+    explicit EssentialTracker(vx_ctx* ctx = nullptr) : EssentialTracker(ctx, Options()) {}
+    EssentialTracker(vx_ctx* ctx, const Options& options) : ctx_(ctx), options_(options) {}
+
+    // Tracking::TrackLastFrame with last_frame_ / current_frame_ as arguments: the reference's return
+    // values (false for a null frame or camera, too few matches, a failed essential estimate, too few
+    // inliers); on success current->SetPose(T_cl * last->Pose()).  Feature positions are narrowed to
+    // float as cv::Point2f does; std::invalid_argument if a coordinate is not float-representable
+    // (the parallax, which the reference takes from the doubles, would differ).
+    bool TrackLastFrame(const Frame::Ptr& last, const Frame::Ptr& current);
+    // Tracking::InitWithSecondFrame up to its parallax gate (:207-245) with init_frame_ /
+    // current_frame_ as arguments: the same sequence with T_lw = identity (init's pose is not read),
+    // then `parallax < 1.0f * M_PI / 180.0f` -> false.  On success current->SetPose(T_cl) and
+    // LastInliers / LastParallax are set (:259-260); landmark creation and the two insertions stay
+    // with KeyFrameLandmarks::CreateKeyFrame.
+    bool EstimateInitialPose(const Frame::Ptr& init, const Frame::Ptr& current);
+
+    int LastInliers() const { return last_inliers_; }        // last_inliers_  (:324; kept on failure)
+    double LastParallax() const { return last_parallax_; }   // last_parallax_ (:325; kept on failure)
+    const vx_track_essential_result& LastResult() const { return last_; }  // every count of the last call
+
+private:
+    bool Run(const Frame::Ptr& last, const Frame::Ptr& current, const double* pose_last7);
+    vx_ctx* ctx_;
+    Options options_;
+    vx_track_essential_result last_{};
+    int last_inliers_ = 0;
+    double last_parallax_ = 0.0;
+    std::vector<float> xy_last_, xy_curr_;
+};
+
+// Tracking::Track() (core/frontend/tracking.cpp:267-279): TrackWithPnP against the last keyframe when
+// there is one, and TrackLastFrame when that fails.  Sequential, as the reference: the fallback is
+// enqueued only once the PnP result is known.
+class FrameTracker {
+public:
+    struct Options {
+        PnPTracker::Options pnp;
+        EssentialTracker::Options essential;
+    };
+    explicit FrameTracker(DeviceMap::Ptr map) : FrameTracker(std::move(map), Options()) {}
+    FrameTracker(DeviceMap::Ptr map, const Options& options);
+
+    // last_keyframe may be null (no PnP attempt, :269); last_frame null -> false (:282-285)
+    bool Track(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current);
+
+    bool UsedFallback() const { return used_fallback_; }     // the last Track() ran TrackLastFrame
+    int LastInliers() const { return used_fallback_ ? essential_.LastInliers() : pnp_.LastInliers(); }
+    double LastParallax() const { return used_fallback_ ? essential_.LastParallax() : pnp_.LastParallax(); }
+    PnPTracker& Pnp() { return pnp_; }
+    EssentialTracker& Essential() { return essential_; }
+
+private:
+    PnPTracker pnp_;
+    EssentialTracker essential_;
+    bool used_fallback_ = false;
+};
+
 }  // namespace visionx

@@ -39,6 +39,24 @@ struct SE3d {
         return {p.x + qw * vx + (qy * vz - qz * vy) + tx, p.y + qw * vy + (qz * vx - qx * vz) + ty,
                 p.z + qw * vz + (qx * vy - qy * vx) + tz};
     }
+    // Sophus SE3 * SE3 (T_cl * T_lw, tracking.cpp:541): the Hamilton product in Eigen's coefficient
+    // order, Sophus's first-order renormalisation q *= 2 / (1 + |q|^2) when |q|^2 != 1, and the
+    // rotated translation — operation for operation what k_track_epose (csrc/track_ess.hip) runs
+    SE3d operator*(const SE3d& b) const {
+        SE3d r;
+        r.qw = qw * b.qw - qx * b.qx - qy * b.qy - qz * b.qz;
+        r.qx = qw * b.qx + qx * b.qw + qy * b.qz - qz * b.qy;
+        r.qy = qw * b.qy + qy * b.qw + qz * b.qx - qx * b.qz;
+        r.qz = qw * b.qz + qz * b.qw + qx * b.qy - qy * b.qx;
+        const double n2 = r.qx * r.qx + r.qy * r.qy + r.qz * r.qz + r.qw * r.qw;
+        if (n2 != 1.0) {
+            const double s = 2.0 / (1.0 + n2);
+            r.qx *= s; r.qy *= s; r.qz *= s; r.qw *= s;
+        }
+        const Vec3d t = *this * Vec3d(b.tx, b.ty, b.tz);
+        r.tx = t.x; r.ty = t.y; r.tz = t.z;
+        return r;
+    }
 };
 
 struct ImageU8 {

@@ -1,6 +1,7 @@
 // tracking.cpp — visionx::PnPTracker over vx_track_pnp_host_async / vx_track_pnp_fetch (see tracking.h).
 #include "visionx/tracking.h"
 
+#include <cmath>
 #include <stdexcept>
 #include <string>
 
@@ -50,6 +51,90 @@ bool PnPTracker::TrackWithPnP(const Frame::Ptr& last_keyframe, const Frame::Ptr&
     last_parallax_ = last_.parallax;
     last_inliers_ = last_.pnp.n_inliers;
     return true;
+}
+
+namespace vxhost {
+vx_ctx* ThreadContext();  // feature.cpp
+}
+
+namespace {
+
+// cv::Point2f(position.x(), position.y()) (tracking.cpp:512-513) for every feature
+void NarrowPositions(const std::vector<Feature>& feats, std::vector<float>& xy) {
+    xy.resize(2 * feats.size());
+    for (size_t i = 0; i < feats.size(); ++i) {
+        const float x = (float)feats[i].position.x, y = (float)feats[i].position.y;
+        if ((double)x != feats[i].position.x || (double)y != feats[i].position.y)
+            throw std::invalid_argument("EssentialTracker: feature position is not float-representable");
+        xy[2 * i] = x;
+        xy[2 * i + 1] = y;
+    }
+}
+
+}  // namespace
+
+bool EssentialTracker::Run(const Frame::Ptr& last, const Frame::Ptr& current, const double* pose_last7) {
+    const auto cam = current->GetCamera();  // (:516)
+    if (!cam) return false;
+    const double intr[4] = {cam->fx(), cam->fy(), cam->cx(), cam->cy()};
+    const int n_last = last->Descriptors().rows, n_curr = current->Descriptors().rows;
+    if ((size_t)n_last != last->Features().size() || (size_t)n_curr != current->Features().size())
+        throw std::invalid_argument("EssentialTracker: descriptors / features mismatch");
+    NarrowPositions(last->Features(), xy_last_);
+    NarrowPositions(current->Features(), xy_curr_);
+    vx_track_essential_options o;
+    vx_track_essential_default_options(&o);
+    o.min_matches = options_.min_matches;
+    o.min_inliers = options_.min_inliers;
+    vx_ctx* c = ctx_ ? ctx_ : vxhost::ThreadContext();
+    int rc = vx_track_essential_host_async(c, last->Descriptors().ptr(), n_last, xy_last_.data(),
+                                           current->Descriptors().ptr(), n_curr, xy_curr_.data(), options_.nn_ratio,
+                                           pose_last7, intr, &o);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_essential_host_async: ") + vx_last_error(c));
+    rc = vx_track_essential_fetch(c, &last_, nullptr, nullptr, 0);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_essential_fetch: ") + vx_last_error(c));
+    return last_.status == VX_TRACK_OK;
+}
+
+bool EssentialTracker::TrackLastFrame(const Frame::Ptr& last, const Frame::Ptr& current) {
+    if (!last || !current) return false;  // tracking.cpp:282-285
+    const SE3d L = last->Pose();
+    const double pose_last[7] = {L.qx, L.qy, L.qz, L.qw, L.tx, L.ty, L.tz};
+    if (!Run(last, current, pose_last)) return false;
+    const double* p = last_.pose;  // T_cl * T_lw, composed on the device as SE3d::operator* would
+    SE3d T;
+    T.qx = p[0]; T.qy = p[1]; T.qz = p[2]; T.qw = p[3];
+    T.tx = p[4]; T.ty = p[5]; T.tz = p[6];
+    current->SetPose(T);
+    last_inliers_ = last_.ess.n_inliers;  // (:324-325)
+    last_parallax_ = last_.parallax;
+    return true;
+}
+
+bool EssentialTracker::EstimateInitialPose(const Frame::Ptr& init, const Frame::Ptr& current) {
+    if (!init || !current) return false;
+    if (!Run(init, current, nullptr)) return false;  // T_lw = identity (:200)
+    const double* p = last_.pose;
+    SE3d T;
+    T.qx = p[0]; T.qy = p[1]; T.qz = p[2]; T.qw = p[3];
+    T.tx = p[4]; T.ty = p[5]; T.tz = p[6];
+    current->SetPose(T);  // (:232 -> :541, before the parallax gate, as the reference)
+    const float parallax = (float)last_.parallax;            // (:240)
+    const float min_parallax = 1.0f * M_PI / 180.0f;         // (:241)
+    if (parallax < min_parallax) return false;               // (:242)
+    last_parallax_ = parallax;                               // (:259-260: the float, widened)
+    last_inliers_ = last_.ess.n_inliers;
+    return true;
+}
+
+FrameTracker::FrameTracker(DeviceMap::Ptr map, const Options& options)
+    : pnp_(map, options.pnp), essential_(map ? map->context() : nullptr, options.essential) {}
+
+bool FrameTracker::Track(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current) {
+    used_fallback_ = false;
+    if (last_keyframe && pnp_.TrackWithPnP(last_keyframe, current)) return true;  // tracking.cpp:269-273
+    used_fallback_ = true;
+    return essential_.TrackLastFrame(last_frame, current);                        // (:278)
 }
 
 }  // namespace visionx

@@ -101,6 +101,8 @@ EXPORTS = [
     "vx_dmap_cull_results", "vx_cull_block", "vx_cull_lds_keyframes",
     "vx_keyframe_default_options", "vx_dmap_create_keyframe", "vx_dmap_create_keyframe_host", "vx_dmap_create_results",
     "vx_dmap_keyframe_features", "vx_keyframe_block", "vx_prof_enable64",
+    "vx_track_essential_default_options", "vx_track_essential_async", "vx_track_essential_host_async",
+    "vx_track_essential_fetch",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -190,6 +192,14 @@ def lib():
         L.vx_track_pnp_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.vx_track_pnp_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_track_essential_default_options.restype = None
+        L.vx_track_essential_default_options.argtypes = [C.c_void_p]
+        L.vx_track_essential_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        L.vx_track_essential_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vx_track_essential_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.vx_cull_default_options.restype = None
         L.vx_cull_default_options.argtypes = [C.c_void_p]
         L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -287,6 +297,30 @@ def track_options(min_matches=None, min_inliers=None, max_iterations=None, repro
                  ("seed", seed), ("refine_iterations", refine_iterations)):
         if v is not None:
             o["pnp"][k] = v
+    return o
+
+
+# vx_track_essential_options / vx_track_essential_result (include/vx_slam.h; sizes pinned in csrc/track_ess.hip)
+TRACK_ESS_OPTIONS_DTYPE = np.dtype([("min_matches", "<i4"), ("min_inliers", "<i4"), ("ess", EM_OPTIONS_DTYPE)])
+TRACK_ESS_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("n_good_matches", "<i4"), ("n_pairs", "<i4"),
+                                   ("n_bad_index", "<i4"), ("min_distance", "<f4"), ("parallax", "<f8"),
+                                   ("pose", "<f8", 7), ("ess", EM_RESULT_DTYPE)])
+TRACK_ESSENTIAL_FAILED = 5
+
+
+def track_essential_options(min_matches=None, min_inliers=None, max_iterations=None, threshold=None, confidence=None,
+                            distance_thresh=None, seed=None):
+    """Tracking::Options' gates + findEssentialMat / recoverPose's arguments in Tracking::TrackLastFrame
+    (tracking.h:27-28, tracking.cpp:521-528), any field overridable."""
+    o = np.zeros((), TRACK_ESS_OPTIONS_DTYPE)
+    lib().vx_track_essential_default_options(_p(o))
+    for k, v in (("min_matches", min_matches), ("min_inliers", min_inliers)):
+        if v is not None:
+            o[k] = v
+    for k, v in (("max_iterations", max_iterations), ("threshold", threshold), ("confidence", confidence),
+                 ("distance_thresh", distance_thresh), ("seed", seed)):
+        if v is not None:
+            o["ess"][k] = v
     return o
 
 
@@ -610,6 +644,61 @@ class Context:
         pm = np.zeros(max(cap, 1), np.int32)
         mask = np.zeros(max(cap, 1), np.uint8)
         self._check(lib().vx_track_pnp_fetch(self._h, _p(out), _p(pm), _p(mask), cap))
+        n = int(out[0]["n_pairs"])
+        return out[0], pm[:n].copy(), mask[:n].copy()
+
+    def _xy_rows(self, rows):
+        """a slot number -> (device pointer of its first x, 20, device pointer of its count); a
+        (pointer, stride, count pointer) triple as it is"""
+        if isinstance(rows, (int, np.integer)):
+            return self.slot_keypoints(int(rows)), KEYPOINT_DTYPE.itemsize, self.slot_device(int(rows))[1]
+        return rows
+
+    def track_essential_async(self, last, curr, intr, opts=None, matches=None, pose_last=None):
+        """Tracking::TrackLastFrame after the match (tracking.cpp:291-325, :509-541) on the device.  last /
+        curr: an extraction slot of this context, or (device pointer of the first x, row stride in
+        bytes, device pointer of the int32 row count); matches: None = this context's last
+        match_*_async result (query = last), or (device pointer of MATCH_DTYPE rows, device pointer of
+        the int32 count, capacity); pose_last: T_lw as qx qy qz qw tx ty tz (None: identity).  Nothing
+        synchronises; track_essential_fetch() completes it."""
+        lxy, lstride, ln = self._xy_rows(last)
+        cxy, cstride, cn = self._xy_rows(curr)
+        m_ptr, mn_ptr, m_cap = matches if matches is not None else (None, None, 0)
+        intr = np.ascontiguousarray(intr, np.float64)
+        assert intr.size == 4
+        pose = None if pose_last is None else np.ascontiguousarray(pose_last, np.float64)
+        assert pose is None or pose.size == 7
+        opts = np.ascontiguousarray(track_essential_options() if opts is None else opts, TRACK_ESS_OPTIONS_DTYPE)
+        self._check(lib().vx_track_essential_async(self._h, C.c_void_p(lxy), int(lstride), C.c_void_p(ln),
+                                                   C.c_void_p(cxy), int(cstride), C.c_void_p(cn), C.c_void_p(m_ptr),
+                                                   C.c_void_p(mn_ptr), int(m_cap), None if pose is None else _p(pose),
+                                                   _p(intr), _p(opts)))
+
+    def track_essential_host_async(self, desc_last, last_xy, desc_curr, curr_xy, intr, opts=None, ratio: float = 0.8,
+                                   pose_last=None):
+        """The host-input form (vx_track_essential_host_async, what visionx::EssentialTracker calls): both
+        frames' descriptor rows and positions uploaded in one copy, matched on the device (query =
+        last), then as track_essential_async on that match list."""
+        q = np.ascontiguousarray(desc_last, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(desc_curr, np.uint8).reshape(-1, 32)
+        qxy = np.ascontiguousarray(last_xy, np.float32).reshape(-1, 2)
+        txy = np.ascontiguousarray(curr_xy, np.float32).reshape(-1, 2)
+        assert len(qxy) == len(q) and len(txy) == len(t)
+        intr = np.ascontiguousarray(intr, np.float64)
+        assert intr.size == 4
+        pose = None if pose_last is None else np.ascontiguousarray(pose_last, np.float64)
+        assert pose is None or pose.size == 7
+        opts = np.ascontiguousarray(track_essential_options() if opts is None else opts, TRACK_ESS_OPTIONS_DTYPE)
+        self._check(lib().vx_track_essential_host_async(self._h, _p(q), len(q), _p(qxy), _p(t), len(t), _p(txy), ratio,
+                                                        None if pose is None else _p(pose), _p(intr), _p(opts)))
+
+    def track_essential_fetch(self, cap: int = 8192):
+        """(TRACK_ESS_RESULT_DTYPE record, pair_match int32[n_pairs], recoverPose mask uint8[n_pairs]) of
+        the last track_essential_async: one copy, one synchronisation."""
+        out = np.zeros(1, TRACK_ESS_RESULT_DTYPE)
+        pm = np.zeros(max(cap, 1), np.int32)
+        mask = np.zeros(max(cap, 1), np.uint8)
+        self._check(lib().vx_track_essential_fetch(self._h, _p(out), _p(pm), _p(mask), cap))
         n = int(out[0]["n_pairs"])
         return out[0], pm[:n].copy(), mask[:n].copy()
 

@@ -505,6 +505,46 @@ def make_two_view(seed: int, n: int = 1000, *, outlier_frac: float = 0.3, noise_
             "R": R, "t": t, "t_dir": t / np.linalg.norm(t), "outlier": out}
 
 
+def make_last_frame_scene(seed: int, n_feat: int = 300, *, wrong_frac: float = 0.3, noise_px: float = 0.5,
+                          max_flips: int = 24, width: int = 640, height: int = 480, intr=(FX, FY, CX, CY),
+                          baseline_m: float = 0.15, rot_deg: float = 3.0, z_range=(1.0, 6.0)):
+    """What Tracking::TrackLastFrame (tracking.cpp:281-330) reads: make_two_view's geometry (points seen
+    by the last and the current camera, pixel noise, a fraction `wrong_frac` of the current pixels
+    replaced by random ones) with make_track_scene's descriptor construction (the current frame's
+    keypoints stored in a permuted order, its descriptors random, last feature i's its keypoint's
+    with flips[i] bits flipped), so Match(last, curr) returns `matches` (query i, train train_of[i],
+    distance flips[i]).
+
+    Returns a dict: last_xy, curr_xy (n x 2 float32; curr permuted), train_of (int32), desc_last /
+    desc_curr (n x 32 uint8), flips, matches (MATCH_DTYPE-compatible record array), wrong (bool), intr,
+    the true T_cl (R, t with x_curr = R x_last + t; t_dir = t / |t|), pose_last (a non-trivial T_lw,
+    qx qy qz qw tx ty tz, qw > 0) and R_cw (the rotation of T_cl * T_lw)."""
+    tv = make_two_view(seed, n_feat, outlier_frac=wrong_frac, noise_px=noise_px, width=width, height=height,
+                       intr=intr, baseline_m=baseline_m, rot_deg=rot_deg, z_range=z_range)
+    rng = np.random.default_rng([seed, 0x7E55])
+    perm = rng.permutation(n_feat).astype(np.int32)
+    curr_xy = np.zeros((n_feat, 2), np.float32)
+    curr_xy[perm] = tv["pts_curr"]
+    desc_curr = rng.integers(0, 256, (n_feat, 32), dtype=np.uint8)
+    flips = rng.integers(0, max_flips + 1, n_feat).astype(np.int32)
+    bits = np.unpackbits(desc_curr[perm], axis=1)
+    for i in range(n_feat):
+        bits[i, rng.choice(256, flips[i], replace=False)] ^= 1
+    desc_last = np.packbits(bits, axis=1)
+    matches = np.zeros(n_feat, [("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")])
+    matches["query_idx"] = np.arange(n_feat)
+    matches["train_idx"] = perm
+    matches["distance"] = flips
+    q_lw = quat_from_rotvec(rng.normal(0, 0.4, 3))
+    if q_lw[3] < 0:
+        q_lw = -q_lw
+    pose_last = np.concatenate([q_lw, rng.normal(0, 0.7, 3)])
+    return {"last_xy": tv["pts_last"], "curr_xy": curr_xy, "train_of": perm, "desc_last": desc_last,
+            "desc_curr": desc_curr, "flips": flips, "matches": matches, "wrong": tv["outlier"], "intr": tv["intr"],
+            "R": tv["R"], "t": tv["t"], "t_dir": tv["t_dir"], "pose_last": pose_last,
+            "R_cw": tv["R"] @ quat_to_mat(q_lw)}
+
+
 # --------------------------------------------------------------------------- map culling
 def _project_rows(m, lm_rows, kf_rows):
     """camera-frame points and pixels of landmark rows seen from keyframe rows (R from the quaternion
