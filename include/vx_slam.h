@@ -33,6 +33,8 @@
  *   vx_track_essential_*  <- Tracking::TrackLastFrame after Match() (and InitWithSecondFrame's head):
  *                            distance filter, 2D-2D pairs, findEssentialMat + recoverPose,
  *                            T_cl * T_lw, ComputeParallax       core/frontend/tracking.cpp:281-330
+ *   vx_init_gate_*        <- Tracking::InitWithFirstFrame's gates: feature count, CheckFeatureDistribution,
+ *                            CheckImageQuality                   core/frontend/tracking.cpp:93-139, :177-204
  *   vx_dmap_*             <- visionx::Map (map.h:13-35) kept resident on the device, updated like
  *                            Map::InsertKeyFrame / InsertLandmark / Landmark::AddObservation
  *   vx_dmap_create_keyframe* <- Tracking::CreateKeyFrame's insertion: CreateLandmarksFromDepth,
@@ -920,6 +922,60 @@ int vx_track_essential_host_async(vx_ctx* ctx, const uint8_t* last_desc, int n_l
  * (with *out filled) if an array is given and n_pairs > cap_pairs. */
 int vx_track_essential_fetch(vx_ctx* ctx, vx_track_essential_result* out, int32_t* pair_match, uint8_t* mask,
                              int cap_pairs);
+
+/* ---------------------------------------------------------------- InitWithFirstFrame's gates on the device (init_gate.hip)
+ * <- Tracking::InitWithFirstFrame (tracking.cpp:177-204): the feature count (:179),
+ *    CheckFeatureDistribution's occupancy grid over the keypoints (:93-118) and CheckImageQuality's
+ *    cvtColor(BGR2GRAY) + meanStdDev bounds (:120-139), as two launches over an image and keypoints
+ *    that are already on the device, with one synchronisation, in the fetch.
+ *    Gray is vx_orb_extract's fixed-point level 0; the sums are integers, so the record is bitwise
+ *    repeatable.  mean = sum * (1.0 / N), stddev = sqrt(max(sum_sq * (1.0 / N) - mean * mean, 0)) with
+ *    every operation rounded on its own (meanStdDev's arithmetic: the reciprocal, no fused multiply-add).
+ *    Deviation: cvtColor asserts 3 or 4 channels, so the reference throws on a gray image; here a
+ *    1-channel image is its own gray level, as in vx_orb_extract. */
+typedef struct {              /* Tracking::InitWithFirstFrame, tracking.cpp:177-204 */
+    int32_t min_features;     /* Tracking::Options::min_matches (:179), default 50 */
+    int32_t grid_cols, grid_rows;   /* 5, 5 (:96-97); grid_cols * grid_rows in 1..32 */
+    double min_grid_frac;     /* 0.5 (:117); at byte 16 */
+    double min_mean, max_mean, min_stddev;   /* 30, 225, 20 (:129-135) */
+} vx_init_gate_options;
+
+/* status of vx_init_gate_result: the first gate that fails, in the reference's order */
+#define VX_INIT_OK 0
+#define VX_INIT_FEW_FEATURES 1        /* n_features < min_features                          (tracking.cpp:179) */
+#define VX_INIT_POOR_DISTRIBUTION 2   /* valid_grids < cols * rows * min_grid_frac (double) (tracking.cpp:117) */
+#define VX_INIT_POOR_IMAGE 3          /* mean < min_mean || mean > max_mean || stddev < min_stddev (:129-135) */
+
+typedef struct {
+    int32_t status;             /* VX_INIT_*; every field below is filled whichever gate failed */
+    int32_t n_features;         /* min(*d_n_feat, cap_feat) */
+    int32_t valid_grids;        /* occupied cells (:109-114) */
+    uint32_t grid_mask;         /* bit col * grid_rows + row set: grid[col][row] (:105) */
+    int64_t n_pixels;           /* width * height */
+    uint64_t sum, sum_sq;       /* over the gray level-0 pixels */
+    double mean, stddev;        /* meanStdDev (:126) */
+} vx_init_gate_result;
+
+/* tracking.h:27, tracking.cpp:96-97, :117, :129-135: 50 / 5 x 5 / 0.5 / 30, 225, 20 */
+void vx_init_gate_default_options(vx_init_gate_options* o);
+/* <- tracking.cpp:179-197.  d_img: the device image vx_orb_extract_async takes (channels 1, 3 (BGR) or
+ * 4 (BGRA), row_stride >= width * channels, any base alignment); it is read itself, so the call does
+ * not depend on what was last extracted on ctx.  Keypoints as vx_track_essential_async takes them:
+ * row i = two floats at d_xy + i * xy_stride_bytes (20 for a slot's vx_keypoint rows from
+ * vx_orb_slot_keypoints, 8 for packed float2), min(*d_n_feat, cap_feat) rows.  d_xy may be NULL when
+ * cap_feat is 0.  Enqueued on ctx's stream; no host synchronisation.  VX_ERR_INVALID for a null
+ * pointer, non-positive geometry, channels outside {1, 3, 4}, a short stride or grid_cols * grid_rows
+ * outside 1..32. */
+int vx_init_gate_async(vx_ctx* ctx, const uint8_t* d_img, int width, int height, int channels, int64_t row_stride,
+                       const float* d_xy, int64_t xy_stride_bytes, const int32_t* d_n_feat, int cap_feat,
+                       const vx_init_gate_options* opt);
+/* Host-input form (what visionx::Tracking calls): the image rows and the positions are staged and
+ * uploaded in ONE copy, then as vx_init_gate_async.  May block at its start until the PREVIOUS call's
+ * upload has left the pinned staging block it reuses, as vx_track_essential_host_async. */
+int vx_init_gate_host_async(vx_ctx* ctx, const uint8_t* img, int width, int height, int channels, int64_t row_stride,
+                            const float* xy, int64_t xy_stride_bytes, int n_feat, const vx_init_gate_options* opt);
+/* One device-to-host copy of the record and one synchronisation.  VX_ERR_STATE when nothing was enqueued. */
+int vx_init_gate_fetch(vx_ctx* ctx, vx_init_gate_result* out);
 
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,

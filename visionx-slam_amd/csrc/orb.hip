@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "vx_gray.hpp"
 #include "vx_internal.hpp"
 #include "vx_ktrace.hpp"
 
@@ -94,11 +95,7 @@ __device__ __forceinline__ void stage_lds(T* __restrict__ dst, int n, F load) {
 }
 
 // ------------------------------------------------------------------------------ gray
-// cvtColor BGR2GRAY fixed point (B 1868, G 9617, R 4899, >> 14); 1 channel passes through
-__device__ __forceinline__ uint8_t gray_px(const uint8_t* s, int ch) {
-    if (ch == 1) return s[0];
-    return (uint8_t)((s[0] * 1868 + s[1] * 9617 + s[2] * 4899 + (1 << 13)) >> 14);
-}
+// gray_px: cvtColor BGR2GRAY fixed point, shared with init_gate.hip (vx_gray.hpp)
 
 // INTER_LINEAR_EXACT tap: u16 8.8 horizontal, u32 16.16 vertical, (v + 32768) >> 16
 __device__ __forceinline__ uint8_t lin_px(const uint8_t* r0, const uint8_t* r1, int c0, int c1, int4 cx,

@@ -72,6 +72,8 @@ enum Stage : int {
     kStKfCommit,      // its ordered compactions and the map edit (k_kf_commit)
     kStTrackEPairs,   // TrackLastFrame's filter + 2D-2D pair gather (k_track_epairs)
     kStTrackEPose,    // its T_cl * T_lw (k_track_epose)
+    kStInitSums,      // InitWithFirstFrame's gray sum / sum of squares (k_init_sums)
+    kStInitGate,      // its occupancy grid, meanStdDev and gates (k_init_gate)
     kStCount
 };
 
@@ -248,6 +250,14 @@ struct vx_ctx {
     int te_cap = 0;              // match capacity of the enqueued call (sizes the packed result)
     int te_min_matches = 0, te_min_inliers = 0;
     bool te_valid = false;
+
+    // ---- InitWithFirstFrame's gates on the device (init_gate.hip)
+    vx::DevBuf ig_part, ig_out;  // per-workgroup {sum, sum_sq} slots, the result record
+    vx::PinnedBuf ig_host;       // the fetched record
+    vx::PinnedBuf ig_in_host;    // vx_init_gate_host_async: count + positions + image rows staged for one upload ...
+    vx::DevBuf ig_in;            // ... into one device block
+    hipEvent_t ig_in_event = nullptr;  // (recorded after that upload)
+    bool ig_valid = false;
 
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {

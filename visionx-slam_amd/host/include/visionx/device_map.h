@@ -61,6 +61,14 @@ public:
     // landmarks (in row order, the first at row `first_row`) and the new keyframe enter the row tables
     void Created(int64_t first_row, const std::vector<Landmark::Ptr>& lms, const Frame::Ptr& kf);
 
+    // Map::removeAll (map.cpp, tracking.cpp:480,492): the queued edits and the row tables are dropped
+    // and the resident map is emptied — the vx_dmap behind this object is destroyed and created anew
+    // (which also bounds its id tables), so every user reads handle() per call.  The result-prefetch
+    // setting survives.
+    void removeAll();
+    // vx_dmap_prefetch_results, remembered for the maps removeAll creates (LocalBA::UseDeviceMap turns it on)
+    void PrefetchResults(bool on);
+
     // queued edits to the device (Optimize does this itself)
     void Flush();
     vx_dmap* handle() { return dm_; }
@@ -78,6 +86,7 @@ private:
     void FlushObservations();
     vx_ctx* ctx_ = nullptr;
     vx_dmap* dm_ = nullptr;
+    bool prefetch_ = false;
     inline static const Frame::Ptr kNoFrame{};
     inline static const Landmark::Ptr kNoLandmark{};
     std::vector<Frame::Ptr> frames_;        // by resident keyframe row

@@ -1,0 +1,126 @@
+// frontend.h — visionx::Tracking (core/frontend/tracking.h:17-123, tracking.cpp:19-89, :177-204,
+// :459-499, :562-575) over the MI355X C ABI: the reference's State, Options, constructor,
+// ProcessFrame and GetState, with every body it calls replaced by the device-resident adapter of this
+// directory, composed in the reference's order:
+//
+//   extractor_->Extract(*current_frame_)                                   (:42)
+//   InitWithFirstFrame   the three gates: vx_init_gate_host_async + fetch  (:177-204)
+//   InitWithSecondFrame  EssentialTracker::EstimateInitialPose, then two
+//                        KeyFrameLandmarks::CreateKeyFrame calls           (:206-263; ids: init depth,
+//                                                                           current depth, triangulated)
+//   Track                FrameTracker::Track (PnP, then TrackLastFrame)    (:267-279)
+//   CreateKeyFrame       KeyFrameLandmarks::CreateKeyFrame                 (:577-584)
+//   CullLandmarks / CullKeyFrames   MapCulling                             (:78-81)
+//   local_ba_->Optimize  LocalBA over the DeviceMap                        (:82-84)
+//   HandleTrackingBad / Lost   Map::removeAll + DeviceMap::removeAll       (:477-499)
+//
+// It owns the DeviceMap that mirrors `map`; the map handed to the constructor must be empty (or be
+// mirrored by hand through ResidentMap()).  VisualizeFeatures is not ported.
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "vx_slam.h"
+#include "visionx/culling.h"
+#include "visionx/device_map.h"
+#include "visionx/feature.h"
+#include "visionx/mapping.h"
+#include "visionx/tracking.h"
+
+namespace visionx {
+
+class Tracking {
+public:
+    using Ptr = std::shared_ptr<Tracking>;
+    using KeyFrame = Frame;
+
+    enum class State { INIT = 0, TRACKING_GOOD, TRACKING_BAD, LOST };
+
+    struct Options {  // tracking.h:24-54
+        int min_matches = 50;
+        int min_inliers = 30;
+        int min_keyframe_inliers = 50;
+        double min_parallax = 10.0;
+        double max_reproj_error = 2.0;
+        int min_keyframe_gap = 3;
+        bool enable_culling = false;
+
+        // ===== Map culling =====
+        int min_landmark_observations = 2;
+        int min_landmarks_for_culling = 200;
+        int min_keyframes_for_culling = 3;
+        int max_keyframes = 30;
+        int kf_min_shared_observations = 3;
+        double kf_redundant_ratio = 0.9;
+        double landmark_max_reproj_error = 5.0;
+
+        // ===== Triangulation =====
+        double triangulation_max_reproj_error = 5.0;
+        double triangulation_min_angle_deg = 1.0;
+
+        // ===== Local BA =====
+        bool enable_local_ba = true;
+        int ba_window_size = 5;
+        int ba_iterations = 5;
+        int ba_min_pose_observations = 20;
+        int ba_min_point_observations = 2;
+        double ba_huber_delta = 5.0;
+        double ba_max_reproj_error = 5.0;
+    };
+
+    Tracking(const Options& options, std::shared_ptr<FeatureExtractor> extractor,
+             std::shared_ptr<FeatureMatcher> matcher, std::shared_ptr<Map> map);
+
+    void ProcessFrame(Frame::Ptr frame);
+
+    State GetState() const { return state_; }
+
+    // read-only views of the private members (tracking.h:105-122) and of the last calls
+    int LastInliers() const { return last_inliers_; }
+    double LastParallax() const { return last_parallax_; }
+    const vx_init_gate_result& LastInitGate() const { return last_gate_; }  // the last InitWithFirstFrame's record
+    const Frame::Ptr& LastKeyFrame() const { return last_keyframe_; }
+    const Frame::Ptr& LastFrame() const { return last_frame_; }
+    uint64_t Landmarks() const { return keyframes_.landmark_id_; }          // landmark_id_: the next landmark id
+    const DeviceMap::Ptr& ResidentMap() const { return dmap_; }
+    const LocalBA* LocalBa() const { return local_ba_.get(); }              // null without enable_local_ba
+    const FrameTracker& Tracker() const { return tracker_; }               // UsedFallback(): the last Track() ran TrackLastFrame
+
+private:
+    bool InitWithFirstFrame();
+    bool InitWithSecondFrame();
+    bool Track();
+    void UpdateTrackingState();
+    void HandleTrackingFailure();
+    void HandleTrackingBad();
+    void HandleTrackingLost();
+    void Reset();
+    bool NeedNewKeyFrame() const;
+    void CreateKeyFrame();
+
+    State state_ = State::INIT;
+    Options options_;
+
+    Frame::Ptr init_frame_;
+    Frame::Ptr current_frame_;
+    Frame::Ptr last_frame_;
+    Frame::Ptr last_keyframe_;
+
+    int last_inliers_ = 0;
+    double last_parallax_ = 0.0;
+
+    std::shared_ptr<FeatureExtractor> extractor_;
+    std::shared_ptr<FeatureMatcher> matcher_;
+    std::shared_ptr<Map> map_;
+
+    DeviceMap::Ptr dmap_;
+    FrameTracker tracker_;
+    KeyFrameLandmarks keyframes_;  // holds landmark_id_
+    MapCulling culling_;
+    std::unique_ptr<LocalBA> local_ba_;
+    vx_init_gate_result last_gate_{};
+    std::vector<float> xy_;
+};
+
+}  // namespace visionx

@@ -169,6 +169,30 @@ void DeviceMap::UpdateFeatures(const Frame::Ptr& kf, const std::vector<int>& idx
           "vx_dmap_set_features");
 }
 
+void DeviceMap::PrefetchResults(bool on) {
+    prefetch_ = on;
+    Check(vx_dmap_prefetch_results(dm_, on ? 1 : 0), "vx_dmap_prefetch_results");
+}
+
+void DeviceMap::removeAll() {
+    q_lm_id_.clear();
+    q_lm_pos_.clear();
+    q_lm_bad_.clear();
+    q_lm_obj_.clear();
+    q_ob_lm_.clear();
+    q_ob_kf_.clear();
+    q_ob_fi_.clear();
+    frames_.clear();
+    landmarks_.clear();
+    lm_row_.clear();
+    kf_row_.clear();
+    vx_dmap* fresh = nullptr;
+    Check(vx_dmap_create(ctx_, &fresh), "vx_dmap_create");
+    vx_dmap_destroy(dm_);
+    dm_ = fresh;
+    if (prefetch_) PrefetchResults(true);
+}
+
 void DeviceMap::Mirror(const Map& map) {
     for (const auto& kv : map.KeyFrames()) InsertKeyFrame(kv.second);
     for (const auto& kv : map.Landmarks()) InsertLandmark(kv.second);

@@ -545,7 +545,7 @@ vx_ba_options LocalBA::VxOptions() const {
 
 void LocalBA::UseDeviceMap(std::shared_ptr<DeviceMap> dm) {
     dmap_ = std::move(dm);
-    if (dmap_) check(dmap_->context(), vx_dmap_prefetch_results(dmap_->handle(), 1), "vx_dmap_prefetch_results");
+    if (dmap_) dmap_->PrefetchResults(true);  // (kept by the DeviceMap: it survives DeviceMap::removeAll)
 }
 
 void LocalBA::OptimizeResident(const Frame::Ptr& ref_kf) {

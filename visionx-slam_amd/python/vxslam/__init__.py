@@ -103,6 +103,7 @@ EXPORTS = [
     "vx_dmap_keyframe_features", "vx_keyframe_block", "vx_prof_enable64",
     "vx_track_essential_default_options", "vx_track_essential_async", "vx_track_essential_host_async",
     "vx_track_essential_fetch",
+    "vx_init_gate_default_options", "vx_init_gate_async", "vx_init_gate_host_async", "vx_init_gate_fetch",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -200,6 +201,13 @@ def lib():
         L.vx_track_essential_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                     C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vx_track_essential_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_init_gate_default_options.restype = None
+        L.vx_init_gate_default_options.argtypes = [C.c_void_p]
+        L.vx_init_gate_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
+        L.vx_init_gate_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                              C.c_int64, C.c_int, C.c_void_p]
+        L.vx_init_gate_fetch.argtypes = [C.c_void_p, C.c_void_p]
         L.vx_cull_default_options.restype = None
         L.vx_cull_default_options.argtypes = [C.c_void_p]
         L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -321,6 +329,26 @@ def track_essential_options(min_matches=None, min_inliers=None, max_iterations=N
                  ("distance_thresh", distance_thresh), ("seed", seed)):
         if v is not None:
             o["ess"][k] = v
+    return o
+
+
+# vx_init_gate_options / vx_init_gate_result (include/vx_slam.h; sizes pinned in csrc/init_gate.hip)
+INIT_GATE_OPTIONS_DTYPE = np.dtype([("min_features", "<i4"), ("grid_cols", "<i4"), ("grid_rows", "<i4"), ("pad", "<i4"),
+                                    ("min_grid_frac", "<f8"), ("min_mean", "<f8"), ("max_mean", "<f8"),
+                                    ("min_stddev", "<f8")])
+INIT_GATE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_features", "<i4"), ("valid_grids", "<i4"), ("grid_mask", "<u4"),
+                                   ("n_pixels", "<i8"), ("sum", "<u8"), ("sum_sq", "<u8"), ("mean", "<f8"),
+                                   ("stddev", "<f8")])
+INIT_OK, INIT_FEW_FEATURES, INIT_POOR_DISTRIBUTION, INIT_POOR_IMAGE = range(4)
+
+
+def init_gate_options(**fields):
+    """Tracking::InitWithFirstFrame's constants (tracking.h:27, tracking.cpp:96-97, :117, :129-135), any field
+    overridable: min_features, grid_cols, grid_rows, min_grid_frac, min_mean, max_mean, min_stddev."""
+    o = np.zeros((), INIT_GATE_OPTIONS_DTYPE)
+    lib().vx_init_gate_default_options(_p(o))
+    for k, v in fields.items():
+        o[k] = v
     return o
 
 
@@ -701,6 +729,43 @@ class Context:
         self._check(lib().vx_track_essential_fetch(self._h, _p(out), _p(pm), _p(mask), cap))
         n = int(out[0]["n_pairs"])
         return out[0], pm[:n].copy(), mask[:n].copy()
+
+    def init_gate_async(self, d_img_ptr: int, w: int, h: int, channels: int, row_stride: int, feats, opts=None,
+                        cap_feat: int | None = None):
+        """Tracking::InitWithFirstFrame's gates (tracking.cpp:177-197) on a device image.  feats: an
+        extraction slot of this context, or (device pointer of the first x, row stride in bytes, device
+        pointer of the int32 row count); cap_feat: at most that many rows (default: the slot's capacity;
+        required with a triple).  Nothing synchronises; init_gate_fetch() completes it."""
+        if isinstance(feats, (int, np.integer)) and cap_feat is None:
+            cap_feat = self.slot_device(int(feats))[2]
+        xy, stride, n_ptr = self._xy_rows(feats)
+        assert cap_feat is not None
+        opts = np.ascontiguousarray(init_gate_options() if opts is None else opts, INIT_GATE_OPTIONS_DTYPE)
+        self._check(lib().vx_init_gate_async(self._h, C.c_void_p(d_img_ptr), int(w), int(h), int(channels),
+                                             int(row_stride), C.c_void_p(xy), int(stride), C.c_void_p(n_ptr),
+                                             int(cap_feat), _p(opts)))
+
+    def init_gate_host(self, img: np.ndarray, xy, opts=None, fetch: bool = True):
+        """The host-input form (vx_init_gate_host_async, what visionx::Tracking calls): image rows (H x W
+        or H x W x C uint8, any row stride) and float2 positions uploaded in one copy.  Returns the
+        fetched INIT_GATE_RESULT_DTYPE record (fetch=False: only enqueues)."""
+        assert img.dtype == np.uint8 and img.ndim in (2, 3)
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        if img.strides[1] != ch or (img.ndim == 3 and img.strides[2] != 1) or img.strides[0] < w * ch:
+            img = np.ascontiguousarray(img)
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        opts = np.ascontiguousarray(init_gate_options() if opts is None else opts, INIT_GATE_OPTIONS_DTYPE)
+        self._check(lib().vx_init_gate_host_async(self._h, _p(img), w, h, ch, int(img.strides[0]), _p(xy), 8, len(xy),
+                                                  _p(opts)))
+        return self.init_gate_fetch() if fetch else None
+
+    def init_gate_fetch(self):
+        """the INIT_GATE_RESULT_DTYPE record of the last init_gate_async / init_gate_host: one copy, one
+        synchronisation"""
+        out = np.zeros(1, INIT_GATE_RESULT_DTYPE)
+        self._check(lib().vx_init_gate_fetch(self._h, _p(out)))
+        return out[0]
 
     def match_device_async(self, query, train, ratio: float = 0.8):
         """Match device descriptor sets given as slot_device() triples (possibly of another context)."""

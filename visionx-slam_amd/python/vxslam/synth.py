@@ -545,6 +545,89 @@ def make_last_frame_scene(seed: int, n_feat: int = 300, *, wrong_frac: float = 0
             "R_cw": tv["R"] @ quat_to_mat(q_lw)}
 
 
+def make_sequence(seed: int, n_frames: int = 14, n_pts: int = 350, *, width: int = 640, height: int = 480,
+                  intr=(FX, FY, CX, CY), step_m: float = 1.0, yaw_deg: float = 0.25, z_range=(5.0, 9.5),
+                  depth_share: float = 0.5, noise_px: float = 0.3, max_flips: int = 10, garbage=(), dark=()):
+    """What Tracking::ProcessFrame (tracking.cpp:39-89) reads frame after frame: world points seen by a
+    camera that moves along a straight line with a slowly growing yaw, about `n_pts` of them in view of
+    every frame.
+
+    The camera centres are exactly `step_m` apart.  The default is 1: InitWithSecondFrame takes the
+    unit translation recoverPose returns (:528-541) while CreateLandmarksFromDepth places points at
+    their metric depth (:626-640), so the two only agree in a world whose first baseline is 1 (the
+    TrackLastFrame fallback composes unit steps in the same way).  With fx = 520 and z in `z_range`
+    that is a displacement of 55-105 px a frame.
+
+    Per frame i (frames[i], a dict): xy (n_i x 2 float32: true projection + noise, in a permuted order),
+    desc (n_i x 32 uint8: the point's base row with up to `max_flips` bits flipped, make_track_scene's
+    construction, so two views of a point are at most 2 * max_flips apart and unrelated rows about
+    128), point (int64: the world point behind each feature), depth (height x width uint16:
+    round(z * 5000) at the pixel CreateLandmarksFromDepth reads, (int)(x + 0.5), (int)(y + 0.5), for a
+    share `depth_share` of the features, 0 elsewhere and where two features share a pixel), img
+    (height x width x 3 uint8, a make_frames frame: it passes the quality gate), pose (true T_cw, qx
+    qy qz qw tx ty tz, relative to frame 0).
+    `garbage`: frames whose positions and descriptors are replaced by random ones (nothing matches);
+    `dark`: frames whose image is all zero (only InitWithFirstFrame looks at the image).
+    Returns {"frames", "intr", "width", "height", "points"}."""
+    rng = np.random.default_rng([seed, 0x5E0])
+    fx, fy, cx, cy = intr
+    z0, z1 = z_range
+    d = np.array([0.99, 0.04, 0.08])
+    d /= np.linalg.norm(d)
+    centres = np.arange(n_frames)[:, None] * step_m * d[None, :]
+    # a slab that covers every frame's frustum, thinned until about n_pts points are in view of a frame
+    x_lo, x_hi = -cx / fx * z1 - 1.0, centres[-1, 0] + (width - cx) / fx * z1 + 1.0
+    cand = int(np.ceil(3 * n_pts * (x_hi - x_lo) * fx / (width * z0)))
+    z = rng.uniform(z0, z1 + centres[-1, 2], cand)
+    pts = np.stack([rng.uniform(x_lo, x_hi, cand),
+                    (rng.uniform(-20, height + 20, cand) - cy) / fy * z + rng.uniform(0, 1, cand) * centres[-1, 1], z], -1)
+    seen = 0
+    for c in centres:  # (the yaw is small: the unrotated frustum is close enough for a count)
+        pc = pts - c
+        u, v = fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy
+        seen += np.count_nonzero((pc[:, 2] < 9.9) & (u >= 2) & (u < width - 2) & (v >= 2) & (v < height - 2))
+    total = min(cand, int(round(cand * n_pts * n_frames / max(seen, 1))))
+    pts = pts[:total]
+    base = rng.integers(0, 256, (total, 32), dtype=np.uint8)
+    imgs = make_frames(seed, n_frames, height, width)
+    frames = []
+    for i in range(n_frames):
+        q = quat_from_rotvec(np.array([0.0, np.deg2rad(yaw_deg) * i, 0.002 * i]))
+        R = quat_to_mat(q)
+        t = -R @ centres[i]
+        pc = pts @ R.T + t
+        with np.errstate(divide="ignore", invalid="ignore"):
+            uv = np.stack([fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy], -1)
+        uv = uv + rng.normal(0, noise_px, uv.shape)
+        vis = np.flatnonzero((pc[:, 2] > 0.5) & (pc[:, 2] < 9.9) & (uv[:, 0] >= 2) & (uv[:, 0] < width - 2) &
+                             (uv[:, 1] >= 2) & (uv[:, 1] < height - 2))
+        vis = vis[rng.permutation(len(vis))]
+        xy = uv[vis].astype(np.float32)
+        bits = np.unpackbits(base[vis], axis=1)
+        for k in range(len(vis)):
+            bits[k, rng.choice(256, rng.integers(0, max_flips + 1), replace=False)] ^= 1
+        desc = np.packbits(bits, axis=1)
+        img = imgs[i].copy()
+        if i in garbage:
+            xy = np.stack([rng.uniform(2, width - 2, len(vis)), rng.uniform(2, height - 2, len(vis))], -1).astype(np.float32)
+            desc = rng.integers(0, 256, (len(vis), 32), dtype=np.uint8)
+        if i in dark:
+            img[:] = 0
+        depth = np.zeros((height, width), np.uint16)
+        px = (xy.astype(np.float64) + 0.5).astype(np.int64)
+        flat = px[:, 1] * width + px[:, 0]
+        _, first, count = np.unique(flat, return_index=True, return_counts=True)
+        alone = np.zeros(len(vis), bool)
+        alone[first[count == 1]] = True
+        has = alone & (rng.random(len(vis)) < depth_share)
+        depth[px[has, 1], px[has, 0]] = np.round(pc[vis[has], 2] * 5000.0).astype(np.uint16)
+        if q[3] < 0:
+            q = -q
+        frames.append({"xy": np.ascontiguousarray(xy), "desc": np.ascontiguousarray(desc), "point": vis, "depth": depth,
+                       "img": img, "pose": np.concatenate([q, t])})
+    return {"frames": frames, "intr": np.array(intr, np.float64), "width": width, "height": height, "points": pts}
+
+
 # --------------------------------------------------------------------------- map culling
 def _project_rows(m, lm_rows, kf_rows):
     """camera-frame points and pixels of landmark rows seen from keyframe rows (R from the quaternion
