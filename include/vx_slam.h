@@ -35,6 +35,10 @@
  *                            T_cl * T_lw, ComputeParallax       core/frontend/tracking.cpp:281-330
  *   vx_init_gate_*        <- Tracking::InitWithFirstFrame's gates: feature count, CheckFeatureDistribution,
  *                            CheckImageQuality                   core/frontend/tracking.cpp:93-139, :177-204
+ *   vx_frame_*            <- what a Frame keeps of ORBExtractor::Extract (keypoints_, descriptors_), on the
+ *                            device for the life of the frame    core/feature/orb_extractor.cpp:13-24
+ *   vx_track_frame_*      <- Tracking::Track: TrackWithPnP, else TrackLastFrame, decided on the device
+ *                                                                core/frontend/tracking.cpp:267-279
  *   vx_dmap_*             <- visionx::Map (map.h:13-35) kept resident on the device, updated like
  *                            Map::InsertKeyFrame / InsertLandmark / Landmark::AddObservation
  *   vx_dmap_create_keyframe* <- Tracking::CreateKeyFrame's insertion: CreateLandmarksFromDepth,
@@ -976,6 +980,126 @@ int vx_init_gate_host_async(vx_ctx* ctx, const uint8_t* img, int width, int heig
                             const float* xy, int64_t xy_stride_bytes, int n_feat, const vx_init_gate_options* opt);
 /* One device-to-host copy of the record and one synchronisation.  VX_ERR_STATE when nothing was enqueued. */
 int vx_init_gate_fetch(vx_ctx* ctx, vx_init_gate_result* out);
+
+/* ---------------------------------------------------------------- device-resident frames (frame.hip)
+ * <- what a visionx::Frame keeps of ORBExtractor::Extract (orb_extractor.cpp:13-24: keypoints_ and
+ *    descriptors_, frame.h:16-40) held on the device for as long as the frame lives.  An extraction
+ *    slot belongs to its context and is overwritten by the next extraction into it; a vx_frame is a
+ *    block of its own:
+ *        int32 count[4] {n, overflow, 0, 0} | vx_keypoint rows[cap] | descriptor rows[cap] (32 B each)
+ *    (the layout of a slot's count; the row arrays start on 16-byte boundaries).  n <= cap always:
+ *    `overflow` is set when the source held more rows than cap, and the first cap of them are kept.
+ *    The handle is bound to the device of the context it was created on and may be read by every
+ *    context of that device (order the reader after the writer with vx_stream_wait_ctx /
+ *    vx_event_wait).  Destroying a frame waits for the device (hipFree). */
+typedef struct vx_frame vx_frame;
+int vx_frame_create(vx_ctx* ctx, int cap, vx_frame** out);   /* cap >= 1 */
+void vx_frame_destroy(vx_frame* frame);
+/* <- orb_extractor.cpp:19-24 (the copy out of detectAndCompute's outputs).  One launch of
+ * k_frame_capture on ctx's stream: min(n_slot, cap) keypoint and descriptor rows of `slot` (a valid
+ * extraction slot of ctx) and its count into `frame`; overflow = n_slot > cap or the slot's own
+ * overflow flag.  Nothing synchronises: the count is read on the device. */
+int vx_frame_capture_async(vx_ctx* ctx, int slot, vx_frame* frame);
+/* <- ORBExtractor::Extract (orb_extractor.cpp:8-25) into a frame: the host image (as vx_orb_extract
+ * takes it) is staged in pinned memory and uploaded, extracted into slot VX_MAX_SLOTS - 1 of ctx and
+ * captured.  The frame then holds vx_orb_extract's keypoints and descriptors, byte for byte.
+ * Nothing is waited for after the enqueue; the call may block at its start until the PREVIOUS
+ * vx_frame_extract_host_async / vx_frame_upload_async on ctx has left the pinned staging block. */
+int vx_frame_extract_host_async(vx_ctx* ctx, vx_frame* frame, const vx_orb_params* params, const uint8_t* img,
+                                int width, int height, int channels, int64_t row_stride);
+/* Features that came from elsewhere (a replay extractor): n float2 positions and n 32-byte rows from
+ * the host, staged and uploaded in ONE copy.  The keypoint rows' response, angle and octave are zero.
+ * VX_ERR_CAPACITY when n > cap.  xy / desc may be NULL when n is 0. */
+int vx_frame_upload_async(vx_ctx* ctx, vx_frame* frame, const float* xy, const uint8_t* desc, int n);
+/* The pointers the device-input forms take: &kp[0].x with *stride_bytes = sizeof(vx_keypoint) = 20 is a
+ * valid d_*_xy of vx_track_pnp_async / vx_track_essential_async / vx_init_gate_async /
+ * vx_dmap_create_keyframe; d_desc / d_count / cap go to vx_match_device_async.  Any output may be
+ * NULL.  Stable for the life of the frame. */
+int vx_frame_device(const vx_frame* frame, const float** d_xy, int64_t* stride_bytes, const uint8_t** d_desc,
+                    const int32_t** d_count, int32_t* cap);
+/* One device-to-host copy (count | keypoint rows [| descriptor rows]) and one synchronisation of ctx's
+ * stream.  kp and desc may each be NULL; with desc == NULL the descriptor rows are not copied.
+ * VX_ERR_CAPACITY with *n_out set when n > cap, as vx_orb_fetch.  vx_frame_fetch_ex also returns the
+ * frame's overflow flag (*overflow, may be NULL). */
+int vx_frame_fetch(vx_ctx* ctx, const vx_frame* frame, vx_keypoint* kp, uint8_t* desc, int cap, int* n_out);
+int vx_frame_fetch_ex(vx_ctx* ctx, const vx_frame* frame, vx_keypoint* kp, uint8_t* desc, int cap, int* n_out,
+                      int* overflow);
+
+/* ---------------------------------------------------------------- Tracking::Track() on the device (track_frame.hip)
+ * <- Tracking::Track (tracking.cpp:267-279): TrackWithPnP against the last keyframe (:269-273) and,
+ *    when it fails, TrackLastFrame against the last frame (:278), over device-resident frames as ONE
+ *    stream-ordered sequence with one synchronisation, in the fetch — whichever path sets the pose:
+ *
+ *      Match(last_kf, curr) -> vx_track_pnp_async's chain -> k_track_gate
+ *                           -> Match(last, curr) -> vx_track_essential_async's chain -> k_track_final
+ *
+ *    k_track_gate evaluates vx_track_pnp_fetch's status rule (tracking.cpp:357, :402, :425, :441) on the
+ *    device and writes the query count the fallback's match and pair kernels read: the last frame's
+ *    count when PnP failed (or there is no last keyframe), 0 when it succeeded.  With the gate closed
+ *    the fallback's kernels run as empty launches: no RANSAC hypothesis runs, and the essential record
+ *    is byte for byte what vx_track_essential_async leaves on an empty match list. */
+#define VX_TRACK_PATH_NONE 0       /* Track() returned false: the pose was not set */
+#define VX_TRACK_PATH_PNP 1        /* TrackWithPnP set it (tracking.cpp:443-447) */
+#define VX_TRACK_PATH_ESSENTIAL 2  /* TrackLastFrame set it (tracking.cpp:539-541) */
+
+typedef struct {
+    int32_t path;               /* VX_TRACK_PATH_* */
+    int32_t status;             /* VX_TRACK_OK, or the status of the last path that ran */
+    int32_t n_inliers;          /* of `path`: pnp.pnp.n_inliers or ess.ess.n_inliers; 0 for PATH_NONE */
+    int32_t n_keypoints;        /* the current frame's keypoint count */
+    double parallax;            /* of `path`: pnp.parallax or ess.parallax; 0 for PATH_NONE */
+    double pose[7];             /* of `path`: pnp.pnp.pose or ess.pose (T_cl * T_lw), copied; 0 for PATH_NONE */
+    int32_t pnp_ran;            /* last_kf was given */
+    int32_t ess_ran;            /* the gate was open and `last` was given */
+    vx_track_result pnp;        /* as vx_track_pnp_fetch returns it (status included); zero when !pnp_ran */
+    vx_track_essential_result ess; /* as vx_track_essential_fetch returns it: of the fallback when ess_ran,
+                                      otherwise of an empty match list (n_matches 0, min_distance 100, ess.ok 0) */
+} vx_track_frame_result;
+
+/* <- tracking.cpp:267-330 + :332-455.  last_kf: the last keyframe's frame (its rows are the features of
+ * keyframe last_kf_id of `map`), NULL: no last keyframe, straight to TrackLastFrame (:269).  last: the
+ * last frame, NULL: the fallback fails (:282).  They may be the same handle (the second match is then
+ * the first list's, gated); at least one must be given.  pose_last7 (host): T_lw of `last`, NULL =
+ * identity (InitWithSecondFrame's head, :207-232, is this call with last_kf = NULL and pose_last7 =
+ * NULL).  ratio: the matcher's nn_ratio for both matches.  Options and intr4 as in vx_track_pnp_async /
+ * vx_track_essential_async.  VX_ERR_INVALID for a null argument, a frame of another device, a keyframe
+ * that is not in the map or bad options.
+ * Ordering: as vx_track_pnp_async towards the map (ctx's stream first waits for the map context's).
+ * Frames written on another context: order ctx after it first (vx_stream_wait_ctx), never the host.
+ * Buffers: the call owns both of its match lists and its packed result; the pair and RANSAC scratch
+ * is vx_track_pnp_async's and vx_track_essential_async's (it runs those two calls on ctx, so their
+ * own fetches afterwards see this call's paths).  Everything is stream-ordered and the result is
+ * complete once k_track_final has run, so any call on ctx except another vx_track_frame_async may
+ * run between the enqueue and the fetch (vx_pnp_ransac, vx_essential_ransac, vx_match_*, ...). */
+int vx_track_frame_async(vx_ctx* ctx, vx_dmap* map, uint64_t last_kf_id, const vx_frame* last_kf,
+                         const vx_frame* last, const vx_frame* curr, float ratio, const double* pose_last7,
+                         const double* intr4, const vx_track_options* pnp_opt,
+                         const vx_track_essential_options* ess_opt);
+/* One device-to-host copy of one packed block (result | both paths' pair_match and mask arrays | the
+ * current frame's keypoint rows when curr_kp is given) and one synchronisation.  curr_kp (may be NULL):
+ * the current frame's keypoint rows, *n_kp their count; VX_ERR_CAPACITY (with *out and *n_kp filled)
+ * when the count exceeds cap_kp.  The pair arrays: vx_track_frame_pairs, after the fetch. */
+int vx_track_frame_fetch(vx_ctx* ctx, vx_track_frame_result* out, vx_keypoint* curr_kp, int cap_kp, int* n_kp);
+/* The fetched block's pair arrays of path `which` (0: PnP, 1: essential): pair_match[k] and mask[k] as
+ * vx_track_pnp_fetch / vx_track_essential_fetch return them (either may be NULL).  No device work.
+ * VX_ERR_STATE before a fetch, VX_ERR_CAPACITY when that path's n_pairs > cap_pairs. */
+int vx_track_frame_pairs(vx_ctx* ctx, int which, int32_t* pair_match, uint8_t* mask, int cap_pairs);
+/* The device match list of the PnP match (which = 0: query = last_kf) or the fallback match (1: query =
+ * last; empty when the gate was closed), e.g. for vx_dmap_create_keyframe (tracking.cpp:340 and :863
+ * match the same two frames).  Valid until the next vx_track_frame_async on ctx.  VX_ERR_STATE when
+ * that match was not enqueued (which = 0 without a last keyframe). */
+int vx_track_frame_matches(vx_ctx* ctx, int which, const vx_match** d_matches, const int32_t** d_n, int32_t* cap);
+
+/* <- Tracking::CreateKeyFrame (tracking.cpp:577-584) over a resident frame: vx_dmap_create_keyframe with
+ * the frame's device positions (vx_frame_device) and a HOST depth image (NULL / rows 0: none), which is
+ * staged and uploaded in one copy per keyframe.  d_matches: a device list (vx_track_frame_matches: the
+ * track's own Match(last keyframe, current), tracking.cpp:340 and :863 being the same two frames), or
+ * NULL for ctx's last vx_match_*_async result.  Everything else as vx_dmap_create_keyframe. */
+int vx_dmap_create_keyframe_frame(vx_ctx* ctx, vx_dmap* map, uint64_t kf_id, const double* pose7, const double* intr4,
+                                  const vx_frame* curr, int has_last, uint64_t last_kf_id, const vx_match* d_matches,
+                                  const int32_t* d_n_matches, int cap_matches, const void* depth, int depth_type, int rows,
+                                  int cols, int64_t row_stride, uint64_t first_landmark_id,
+                                  const vx_keyframe_options* opt, vx_keyframe_result* result);
 
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,

@@ -628,6 +628,42 @@ int vx_dmap_create_keyframe_host(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const do
     return create_run(c, m, kf_id, pose7, intr4, in, has_last, last_kf_id, first_landmark_id, opt, result);
 }
 
+int vx_dmap_create_keyframe_frame(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4,
+                                  const vx_frame* curr, int has_last, uint64_t last_kf_id, const vx_match* d_matches,
+                                  const int32_t* d_n_matches, int cap_matches, const void* depth, int depth_type, int rows,
+                                  int cols, int64_t row_stride, uint64_t first_landmark_id,
+                                  const vx_keyframe_options* opt, vx_keyframe_result* result) {
+    if (!c) return VX_ERR_INVALID;
+    int rc;
+    if ((rc = check_common(c, m, pose7, opt, result, "vx_dmap_create_keyframe_frame"))) return rc;
+    if (!curr || !curr->block.p || curr->device != c->device)
+        return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe_frame: no frame, or a frame of another device");
+    const bool has_depth = depth && rows > 0 && cols > 0;
+    const void* d_depth = nullptr;
+    if (has_depth) {
+        if (depth_type < VX_DEPTH_U16 || depth_type > VX_DEPTH_F64)
+            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", depth_type);
+        if (row_stride < (int64_t)cols * depth_elem(depth_type))
+            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
+        VX_HIP(c, hipSetDevice(c->device));
+        // the depth image is the one thing that still comes from the host: one copy per keyframe,
+        // through the staging vx_dmap_create_keyframe_host uses (and its event)
+        auto& K = m->create;
+        const size_t d_bytes = (size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(depth_type), bytes = align64(d_bytes);
+        if (K.in_event) VX_HIP(c, hipEventSynchronize(K.in_event));
+        else VX_HIP(c, hipEventCreateWithFlags(&K.in_event, hipEventDisableTiming));
+        VX_HIP(c, K.in_host.ensure(bytes));
+        VX_HIP(c, K.in.ensure(bytes));
+        std::memcpy(K.in_host.p, depth, d_bytes);
+        VX_HIP(c, hipMemcpyAsync(K.in.p, K.in_host.p, bytes, hipMemcpyHostToDevice, c->stream));
+        VX_HIP(c, hipEventRecord(K.in_event, c->stream));
+        d_depth = K.in.p;
+    }
+    return vx_dmap_create_keyframe(c, m, kf_id, pose7, intr4, &curr->kp()->x, (int64_t)sizeof(vx_keypoint), curr->count(),
+                                   curr->cap, has_last, last_kf_id, d_matches, d_n_matches, cap_matches, d_depth, depth_type,
+                                   has_depth ? rows : 0, has_depth ? cols : 0, row_stride, first_landmark_id, opt, result);
+}
+
 int vx_dmap_create_results(vx_dmap* m, int cap, vx_keyframe_landmark* records, int* n) {
     if (!m) return VX_ERR_INVALID;
     const auto& R = m->create.rec;

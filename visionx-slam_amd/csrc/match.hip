@@ -365,15 +365,15 @@ int knn_rows_launch(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, c
     }
 }
 
-int match_enqueue(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, const uint8_t* dt,
-                  const int* dnt, int nt_host, int q_cap, int t_cap, float ratio) {
+}  // namespace
+
+// the launches of one match into a caller's list (vx_internal.hpp)
+int match_enqueue_to(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, const uint8_t* dt, const int* dnt,
+                     int nt_host, int q_cap, int t_cap, float ratio, vx_match* out, int* out_count) {
     int rc;
     const int n_chunks = (t_cap + kTC - 1) / kTC;
     const int q_stride = q_cap;
     VX_HIP(c, c->partial.ensure((size_t)n_chunks * q_stride * sizeof(uint2) + (size_t)q_cap * sizeof(unsigned) + 16));
-    VX_HIP(c, c->matches.ensure((size_t)std::max(q_cap, 1) * sizeof(vx_match)));
-    VX_HIP(c, c->match_count.ensure(16));
-    c->match_cap = q_cap;
     static const bool chunked = [] {
         const char* e = getenv("VX_MATCH_CHUNKED");
         return e && e[0] == '1';
@@ -383,9 +383,8 @@ int match_enqueue(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, con
         if ((rc = knn_rows_launch(c, dq, dnq, nq_host, dt, dnt, nt_host, q_cap, ratio, best))) return rc;
         ProfScope ps(c, kStMatchMerge);
         hipLaunchKernelGGL(k_knn_compact, dim3(1), dim3(kMergeBlock), 0, c->stream, best, dnq, nq_host,
-                           c->matches.as<vx_match>(), c->match_count.as<int>());
+                           out, out_count);
         VX_LAUNCH_CHECK(c, "k_knn_compact");
-        c->match_valid = true;
         return VX_OK;
     }
     VX_HIP(c, launch(c, kStMatchPartial, k_knn_partial, dim3((q_cap + kQB - 1) / kQB, n_chunks), dim3(kQB), 0,
@@ -397,11 +396,24 @@ int match_enqueue(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, con
                            dnq, nq_host, dnt, nt_host, q_stride, ratio, best);
         VX_LAUNCH_CHECK(c, "k_knn_merge");
         hipLaunchKernelGGL(k_knn_compact, dim3(1), dim3(kMergeBlock), 0, c->stream, best, dnq, nq_host,
-                           c->matches.as<vx_match>(), c->match_count.as<int>());
+                           out, out_count);
         VX_LAUNCH_CHECK(c, "k_knn_compact");
     }
-    c->match_valid = true;
     return VX_OK;
+}
+
+namespace {
+
+// the context's own list: what vx_match_slots_async / vx_match_device_async / vx_match_knn2_ratio fill
+int match_enqueue(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, const uint8_t* dt,
+                  const int* dnt, int nt_host, int q_cap, int t_cap, float ratio) {
+    VX_HIP(c, c->matches.ensure((size_t)std::max(q_cap, 1) * sizeof(vx_match)));
+    VX_HIP(c, c->match_count.ensure(16));
+    c->match_cap = q_cap;
+    const int rc = match_enqueue_to(c, dq, dnq, nq_host, dt, dnt, nt_host, q_cap, t_cap, ratio,
+                                    c->matches.as<vx_match>(), c->match_count.as<int>());
+    if (rc == VX_OK) c->match_valid = true;
+    return rc;
 }
 
 int match_batch_enqueue(vx_ctx* c, const PairTab& tab, int n_pairs, int q_cap, int t_cap, float ratio) {

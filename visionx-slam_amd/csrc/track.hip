@@ -206,12 +206,10 @@ __global__ void __launch_bounds__(kBlock) k_track_pairs(TrackArgs a) {
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// packed result block: vx_track_result | pair_match[cap] | mask[cap]
-size_t off_pair_match() { return align16(sizeof(vx_track_result)); }
-size_t off_mask(int cap) { return off_pair_match() + align16((size_t)cap * sizeof(int32_t)); }
-size_t packed_bytes(int cap) { return off_mask(cap) + align16((size_t)cap); }
+// packed result block: vx_track_result | pair_match[cap] | mask[cap] (track_common.hpp)
+size_t off_pair_match() { return trk::off_pair_match<vx_track_result>(); }
+size_t off_mask(int cap) { return trk::off_mask<vx_track_result>(cap); }
+size_t packed_bytes(int cap) { return trk::packed_bytes<vx_track_result>(cap); }
 
 }  // namespace
 }  // namespace vx
@@ -379,13 +377,7 @@ int vx_track_pnp_fetch(vx_ctx* c, vx_track_result* out, int32_t* pair_match, uin
     if (c->prof) prof_collect(c);
     const uint8_t* h = static_cast<const uint8_t*>(c->tk_host.p);
     std::memcpy(out, h, sizeof *out);
-    bool finite = true;  // R = Rodrigues(rvec) is finite exactly when the pose is (tracking.cpp:441)
-    for (int k = 0; k < 7; ++k) finite &= std::isfinite(out->pnp.pose[k]);
-    if (out->n_good_matches < c->tk_min_matches) out->status = VX_TRACK_FEW_MATCHES;
-    else if (out->n_pairs < c->tk_min_inliers) out->status = VX_TRACK_FEW_PAIRS;
-    else if (!out->pnp.ok || out->pnp.n_inliers < c->tk_min_inliers) out->status = VX_TRACK_PNP_FAILED;
-    else if (!finite) out->status = VX_TRACK_BAD_ROTATION;
-    else out->status = VX_TRACK_OK;
+    out->status = trk::pnp_status(*out, c->tk_min_matches, c->tk_min_inliers);  // (track_common.hpp)
     const int np = out->n_pairs;
     if ((pair_match || inlier_mask) && np > cap_pairs)
         return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);

@@ -12,6 +12,41 @@ namespace trk {
 constexpr int kBlock = 1024;
 constexpr int kWaves = kBlock / 64;
 
+// The packed result block of vx_track_pnp_async / vx_track_essential_async (R = its record):
+// R | pair_match[cap] | mask[cap], each part on a 16-byte boundary.
+__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+template <class R>
+__host__ __device__ inline size_t off_pair_match() { return align16(sizeof(R)); }
+template <class R>
+__host__ __device__ inline size_t off_mask(int cap) { return off_pair_match<R>() + align16((size_t)cap * sizeof(int32_t)); }
+template <class R>
+__host__ __device__ inline size_t packed_bytes(int cap) { return off_mask<R>(cap) + align16((size_t)cap); }
+
+// The status rules the fetches apply on the host and k_track_gate / k_track_final (track_frame.hip)
+// on the device: ONE statement of each, in the order of the reference's return statements.
+// x - x is 0 exactly when x is finite (inf - inf and NaN - NaN are NaN), on either side.  That holds under
+// IEEE arithmetic only: the library is built without -ffast-math / -ffinite-math-only (Makefile), which
+// would let the compiler fold the test to true here as it would fold std::isfinite.
+__host__ __device__ inline bool pose_finite(const double* pose7) {
+    bool finite = true;  // R = Rodrigues(rvec) is finite exactly when the pose is (tracking.cpp:441)
+    for (int k = 0; k < 7; ++k) finite &= (pose7[k] - pose7[k]) == 0.0;
+    return finite;
+}
+// TrackWithPnP (tracking.cpp:357, :402, :425, :441)
+__host__ __device__ inline int pnp_status(const vx_track_result& r, int min_matches, int min_inliers) {
+    if (r.n_good_matches < min_matches) return VX_TRACK_FEW_MATCHES;
+    if (r.n_pairs < min_inliers) return VX_TRACK_FEW_PAIRS;
+    if (!r.pnp.ok || r.pnp.n_inliers < min_inliers) return VX_TRACK_PNP_FAILED;
+    if (!pose_finite(r.pnp.pose)) return VX_TRACK_BAD_ROTATION;
+    return VX_TRACK_OK;
+}
+// TrackLastFrame (tracking.cpp:306, :317)
+__host__ __device__ inline int ess_status(const vx_track_essential_result& r, int min_matches, int min_inliers) {
+    if (r.n_good_matches < min_matches) return VX_TRACK_FEW_MATCHES;
+    if (!r.ess.ok || r.ess.n_inliers < min_inliers) return VX_TRACK_ESSENTIAL_FAILED;
+    return VX_TRACK_OK;
+}
+
 // Exclusive rank of this thread's flag among the block's flags (thread order) and their total.
 // Two barriers: the wave counts are read by everyone before the next call rewrites them.
 __device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int* total) {

@@ -219,12 +219,10 @@ __global__ void __launch_bounds__(64) k_track_epose(EPoseArgs a) {
     for (int k = 0; k < 7; ++k) a.res->pose[k] = out[k];
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// packed result block: vx_track_essential_result | pair_match[cap] | mask[cap]
-size_t off_pair_match() { return align16(sizeof(vx_track_essential_result)); }
-size_t off_mask(int cap) { return off_pair_match() + align16((size_t)cap * sizeof(int32_t)); }
-size_t packed_bytes(int cap) { return off_mask(cap) + align16((size_t)cap); }
+// packed result block: vx_track_essential_result | pair_match[cap] | mask[cap] (track_common.hpp)
+size_t off_pair_match() { return trk::off_pair_match<vx_track_essential_result>(); }
+size_t off_mask(int cap) { return trk::off_mask<vx_track_essential_result>(cap); }
+size_t packed_bytes(int cap) { return trk::packed_bytes<vx_track_essential_result>(cap); }
 
 bool stride_ok(int64_t s) { return s >= 8 && !(s & 3); }
 
@@ -387,9 +385,7 @@ int vx_track_essential_fetch(vx_ctx* c, vx_track_essential_result* out, int32_t*
     if (c->prof) prof_collect(c);
     const uint8_t* h = static_cast<const uint8_t*>(c->te_host.p);
     std::memcpy(out, h, sizeof *out);
-    if (out->n_good_matches < c->te_min_matches) out->status = VX_TRACK_FEW_MATCHES;                       // (:306)
-    else if (!out->ess.ok || out->ess.n_inliers < c->te_min_inliers) out->status = VX_TRACK_ESSENTIAL_FAILED;  // (:317)
-    else out->status = VX_TRACK_OK;
+    out->status = trk::ess_status(*out, c->te_min_matches, c->te_min_inliers);  // (:306, :317; track_common.hpp)
     const int np = out->n_pairs;
     if ((pair_match || mask) && np > cap_pairs)
         return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);

@@ -1,0 +1,309 @@
+// track_frame.hip — Tracking::Track (core/frontend/tracking.cpp:267-279) over device-resident frames as
+// one stream-ordered sequence (vx_track_frame_async / vx_track_frame_fetch).
+//
+// The reference tries TrackWithPnP against the last keyframe (:269-273) and, when that returns false,
+// TrackLastFrame against the last frame (:278).  Decided on the host, a fallback frame is two matches,
+// two uploads and two synchronisations.  Here the decision is taken on the device:
+//
+//   Match(last_kf, curr)  -> k_track_pairs -> k_pnp_hyp -> k_pnp_refine      [vx_track_pnp_async]
+//   k_track_gate (1 workgroup)
+//   Match(last, curr)     -> k_track_epairs -> k_em_* -> k_track_epose       [vx_track_essential_async]
+//   k_track_final
+//
+// k_track_gate applies trk::pnp_status (track_common.hpp: the rule vx_track_pnp_fetch applies on the
+// host, tracking.cpp:357, :402, :425, :441) to the PnP record and writes the GATED query count: the last
+// frame's count when PnP failed or there is no last keyframe, 0 when it succeeded.  The fallback's
+// match reads it as its query count and k_track_epairs as the last frame's row count; every kernel
+// behind them is driven by device-side counts already, so with the gate closed they run as empty
+// launches (no kernel changes for this): the match list is empty, the essential problem record says
+// {0, 0}, k_em_hyp runs no hypothesis, and the record is what vx_track_essential_async leaves on an
+// empty match list.  When the last keyframe IS the last frame (the frame after a keyframe) the second
+// match is not enqueued: list 1 is list 0's rows under a gated count the gate writes.
+//
+// k_track_final packs what the fetch brings down in one copy:
+//   vx_track_frame_result | pair_match0 | mask0 | pair_match1 | mask1 | the current frame's keypoint rows
+// One lane writes the head (path, status, inliers, parallax, pose: COPIED from the path that set the
+// pose, never recomputed) and the two status fields; the grid copies the two records, the pair arrays
+// up to their device-side counts and the keypoint rows (grid_copy_range: 16-byte vectors).
+//
+// Both kernels are bound by launch latency, not bandwidth: the gate reads one record and writes 16
+// bytes; the final kernel moves 464 B of records, 5 B a pair and 20 B a keypoint (about 50 KB at 2000
+// features).  Resources (-Rpass-analysis=kernel-resource-usage, gfx950): k_track_gate 10 VGPRs / 34 SGPRs,
+// k_track_final 28 VGPRs / 56 SGPRs; no LDS, no scratch.
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+
+#include "vx_internal.hpp"
+#include "dmap.hpp"
+#include "track_common.hpp"
+#include "vx_rows.hpp"
+
+namespace vx {
+namespace {
+
+constexpr int kGateBlock = 64;
+constexpr int kFinalBlock = 256;
+constexpr int kFinalMaxWg = 64;
+
+using trk::align16;
+
+struct GateArgs {
+    const vx_track_result* pnp;  // NULL: no last keyframe
+    int min_matches, min_inliers;
+    const int* n_last;           // NULL: no last frame
+    int cap_last;
+    const int* n_matches0;       // list 0's count, when list 1 shares its rows (else NULL)
+    int* n_matches1;             // ... and list 1's gated count
+    int* gate;                   // {gated query count, PnP status, gate open, 0}
+};
+
+// One workgroup; one lane has all the work (a record read, a rule, four stores)
+__global__ void __launch_bounds__(kGateBlock) k_track_gate(GateArgs a) {
+    if (threadIdx.x != 0) return;
+    const int status = a.pnp ? trk::pnp_status(*a.pnp, a.min_matches, a.min_inliers) : VX_TRACK_OK;
+    const bool open = !a.pnp || status != VX_TRACK_OK;  // (:269-273)
+    a.gate[0] = open && a.n_last ? min(max(*a.n_last, 0), a.cap_last) : 0;
+    a.gate[1] = status;
+    a.gate[2] = open ? 1 : 0;
+    a.gate[3] = 0;
+    if (a.n_matches0) *a.n_matches1 = open ? *a.n_matches0 : 0;
+}
+
+struct FinalArgs {
+    const uint8_t* tk;   // vx_track_pnp_async's packed block (NULL: no last keyframe)
+    int tk_cap;
+    const uint8_t* te;   // vx_track_essential_async's packed block
+    int te_cap;
+    const int* gate;
+    int has_last;
+    int ess_min_matches, ess_min_inliers;
+    const uint8_t* kp;   // the current frame's keypoint rows
+    const int* n_kp;
+    int cap_kp;
+    uint8_t* out;
+    size_t o_pm0, o_mask0, o_pm1, o_mask1, o_kp;
+};
+
+__global__ void __launch_bounds__(kFinalBlock) k_track_final(FinalArgs a) {
+    const size_t t = (size_t)blockIdx.x * kFinalBlock + threadIdx.x, nt = (size_t)gridDim.x * kFinalBlock;
+    vx_track_frame_result* out = reinterpret_cast<vx_track_frame_result*>(a.out);
+    const vx_track_essential_result* er = reinterpret_cast<const vx_track_essential_result*>(a.te);
+    // the records without their first dword (status: written below by the lane that evaluates it)
+    uint32_t* o_pnp = reinterpret_cast<uint32_t*>(&out->pnp);
+    if (a.tk) {
+        const vx_track_result* pr = reinterpret_cast<const vx_track_result*>(a.tk);
+        grid_copy_range(o_pnp + 1, reinterpret_cast<const uint32_t*>(pr) + 1, sizeof(vx_track_result) - 4, t, nt);
+        const int np = min(max(pr->n_pairs, 0), a.tk_cap);
+        grid_copy_range(a.out + a.o_pm0, a.tk + trk::off_pair_match<vx_track_result>(), (size_t)np * 4, t, nt);
+        grid_copy_range(a.out + a.o_mask0, a.tk + trk::off_mask<vx_track_result>(a.tk_cap), ((size_t)np + 3) & ~(size_t)3, t, nt);
+    } else {
+        for (size_t k = 1 + t; k < sizeof(vx_track_result) / 4; k += nt) o_pnp[k] = 0;
+    }
+    grid_copy_range(reinterpret_cast<uint32_t*>(&out->ess) + 1, reinterpret_cast<const uint32_t*>(er) + 1,
+                    sizeof(vx_track_essential_result) - 4, t, nt);
+    const int ne = min(max(er->n_pairs, 0), a.te_cap);
+    grid_copy_range(a.out + a.o_pm1, a.te + trk::off_pair_match<vx_track_essential_result>(), (size_t)ne * 4, t, nt);
+    grid_copy_range(a.out + a.o_mask1, a.te + trk::off_mask<vx_track_essential_result>(a.te_cap), ((size_t)ne + 3) & ~(size_t)3, t, nt);
+    const int nk = min(max(*a.n_kp, 0), a.cap_kp);
+    grid_copy_range(a.out + a.o_kp, a.kp, (size_t)nk * sizeof(vx_keypoint), t, nt);
+    if (t != 0) return;
+
+    const int pnp_ran = a.tk ? 1 : 0, open = a.gate[2];
+    const int ess_ran = open && a.has_last ? 1 : 0;
+    const int pnp_st = a.gate[1];
+    const int ess_st = trk::ess_status(*er, a.ess_min_matches, a.ess_min_inliers);  // (:306, :317)
+    out->pnp.status = pnp_ran ? pnp_st : 0;
+    out->ess.status = ess_st;
+    int path = VX_TRACK_PATH_NONE, status, n_inliers = 0;
+    double parallax = 0.0, pose[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (pnp_ran && pnp_st == VX_TRACK_OK) {  // (:269-273)
+        const vx_track_result* pr = reinterpret_cast<const vx_track_result*>(a.tk);
+        path = VX_TRACK_PATH_PNP;
+        status = VX_TRACK_OK;
+        n_inliers = pr->pnp.n_inliers;
+        parallax = pr->parallax;
+        for (int k = 0; k < 7; ++k) pose[k] = pr->pnp.pose[k];
+    } else if (ess_ran) {  // (:278)
+        status = ess_st;
+        if (ess_st == VX_TRACK_OK) {
+            path = VX_TRACK_PATH_ESSENTIAL;
+            n_inliers = er->ess.n_inliers;
+            parallax = er->parallax;
+            for (int k = 0; k < 7; ++k) pose[k] = er->pose[k];
+        }
+    } else {
+        status = pnp_st;  // no last frame (:282): PnP's failure stands
+    }
+    out->path = path;
+    out->status = status;
+    out->n_inliers = n_inliers;
+    out->n_keypoints = nk;
+    out->parallax = parallax;
+    for (int k = 0; k < 7; ++k) out->pose[k] = pose[k];
+    out->pnp_ran = pnp_ran;
+    out->ess_ran = ess_ran;
+}
+
+}  // namespace
+}  // namespace vx
+
+using namespace vx;
+
+extern "C" {
+
+int vx_track_frame_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const vx_frame* last_kf, const vx_frame* last,
+                         const vx_frame* curr, float ratio, const double* pose_last7, const double* intr4,
+                         const vx_track_options* pnp_opt, const vx_track_essential_options* ess_opt) {
+    if (!c) return VX_ERR_INVALID;
+    if (!curr || !curr->block.p || !intr4 || !ess_opt) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: null argument");
+    if (!last_kf && !last) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: neither a last keyframe nor a last frame");
+    if (last_kf && (!m || !pnp_opt)) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: a last keyframe without a map / options");
+    for (const vx_frame* f : {last_kf, last, curr})
+        if (f && (!f->block.p || f->device != c->device))
+            return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: frame and context on different devices");
+    if (last_kf && m->kf_index.find(last_kf_id) == m->kf_index.end())
+        return set_error(c, VX_ERR_INVALID, "keyframe %llu is not in the map", (unsigned long long)last_kf_id);
+    VX_HIP(c, hipSetDevice(c->device));
+    c->tf_valid = c->tf_fetched = false;
+    c->tf_cap[0] = c->tf_cap[1] = 0;
+
+    // The fallback's query side when there is no last frame: the current frame's rows under a gated
+    // count of 0 (never read), so the essential record is the empty one in every case.
+    const vx_frame* q1 = last ? last : curr;
+    const bool shared = last_kf && last_kf == last;  // list 1 = list 0's rows under a gated count
+    const int cap0 = last_kf ? last_kf->cap : 0, cap1 = q1->cap;
+    VX_HIP(c, c->tf_count.ensure(32));
+    VX_HIP(c, c->tf_gate.ensure(16));
+    if (last_kf) VX_HIP(c, c->tf_matches[0].ensure((size_t)cap0 * sizeof(vx_match)));
+    if (!shared) VX_HIP(c, c->tf_matches[1].ensure((size_t)cap1 * sizeof(vx_match)));
+    int32_t* n0 = c->tf_count.as<int32_t>();
+    int32_t* n1 = n0 + 4;
+    int32_t* gate = c->tf_gate.as<int32_t>();
+    vx_match* list0 = c->tf_matches[0].as<vx_match>();
+    vx_match* list1 = shared ? list0 : c->tf_matches[1].as<vx_match>();
+    const float* curr_xy = &curr->kp()->x;
+    const int64_t stride = (int64_t)sizeof(vx_keypoint);
+    int rc;
+
+    // 1 + 2: Match(last_kf, curr) and TrackWithPnP's chain on it (:340-455)
+    if (last_kf) {
+        if ((rc = match_enqueue_to(c, last_kf->desc(), last_kf->count(), cap0, curr->desc(), curr->count(), curr->cap, cap0,
+                                   curr->cap, ratio, list0, n0)))
+            return rc;
+        if ((rc = vx_track_pnp_async(c, m, last_kf_id, curr_xy, stride, curr->count(), list0, n0, cap0, intr4, pnp_opt)))
+            return rc;
+    }
+    // 3: the decision of :269-273
+    GateArgs g{};
+    g.pnp = last_kf ? c->tk_out.as<vx_track_result>() : nullptr;
+    g.min_matches = last_kf ? pnp_opt->min_matches : 0;
+    g.min_inliers = last_kf ? pnp_opt->min_inliers : 0;
+    g.n_last = last ? last->count() : nullptr;
+    g.cap_last = last ? last->cap : 0;
+    g.n_matches0 = shared ? n0 : nullptr;
+    g.n_matches1 = n1;
+    g.gate = gate;
+    VX_HIP(c, launch(c, kStTrackGate, k_track_gate, dim3(1), dim3(kGateBlock), 0, c->stream, g));
+    // 4 + 5: Match(last, curr) under the gated count and TrackLastFrame's chain on it (:287-325)
+    if (!shared &&
+        (rc = match_enqueue_to(c, q1->desc(), gate, cap1, curr->desc(), curr->count(), curr->cap, cap1, curr->cap, ratio,
+                               list1, n1)))
+        return rc;
+    if ((rc = vx_track_essential_async(c, &q1->kp()->x, stride, gate, curr_xy, stride, curr->count(), list1, n1, cap1,
+                                       pose_last7, intr4, ess_opt)))
+        return rc;
+    // 6: the head and the packed block
+    const int tk_cap = last_kf ? c->tk_cap : 0, te_cap = c->te_cap;
+    FinalArgs f{};
+    f.tk = last_kf ? c->tk_out.as<uint8_t>() : nullptr;
+    f.tk_cap = tk_cap;
+    f.te = c->te_out.as<uint8_t>();
+    f.te_cap = te_cap;
+    f.gate = gate;
+    f.has_last = last ? 1 : 0;
+    f.ess_min_matches = ess_opt->min_matches;
+    f.ess_min_inliers = ess_opt->min_inliers;
+    f.kp = reinterpret_cast<const uint8_t*>(curr->kp());
+    f.n_kp = curr->count();
+    f.cap_kp = curr->cap;
+    f.o_pm0 = align16(sizeof(vx_track_frame_result));
+    f.o_mask0 = f.o_pm0 + align16((size_t)tk_cap * 4);
+    f.o_pm1 = f.o_mask0 + align16((size_t)tk_cap);
+    f.o_mask1 = f.o_pm1 + align16((size_t)te_cap * 4);
+    f.o_kp = f.o_mask1 + align16((size_t)te_cap);
+    const size_t bytes = f.o_kp + align16((size_t)curr->cap * sizeof(vx_keypoint));
+    VX_HIP(c, c->tf_out.ensure(bytes));
+    f.out = c->tf_out.as<uint8_t>();
+    const size_t items = ((size_t)curr->cap * sizeof(vx_keypoint)) / 16 + 1;
+    const int grid = (int)std::min<size_t>(kFinalMaxWg, (items + kFinalBlock - 1) / kFinalBlock);
+    VX_HIP(c, launch(c, kStTrackFinal, k_track_final, dim3(std::max(grid, 1)), dim3(kFinalBlock), 0, c->stream, f));
+    c->tf_cap[0] = cap0;
+    c->tf_cap[1] = cap1;
+    c->tf_pair_cap[0] = tk_cap;
+    c->tf_pair_cap[1] = te_cap;
+    c->tf_cap_kp = curr->cap;
+    c->tf_list1_own = !shared;
+    c->tf_valid = true;
+    return VX_OK;
+}
+
+int vx_track_frame_fetch(vx_ctx* c, vx_track_frame_result* out, vx_keypoint* curr_kp, int cap_kp, int* n_kp) {
+    if (!c || !out) return c ? set_error(c, VX_ERR_INVALID, "vx_track_frame_fetch: null result") : VX_ERR_INVALID;
+    if (curr_kp && (!n_kp || cap_kp < 0)) return set_error(c, VX_ERR_INVALID, "vx_track_frame_fetch: keypoints without a count / capacity");
+    if (!c->tf_valid) return set_error(c, VX_ERR_STATE, "no vx_track_frame_async enqueued");
+    VX_HIP(c, hipSetDevice(c->device));
+    const size_t o_pm0 = align16(sizeof(vx_track_frame_result));
+    const size_t o_kp = o_pm0 + align16((size_t)c->tf_pair_cap[0] * 4) + align16((size_t)c->tf_pair_cap[0]) +
+                        align16((size_t)c->tf_pair_cap[1] * 4) + align16((size_t)c->tf_pair_cap[1]);
+    // the keypoint rows are the block's tail: copied only when asked for
+    const size_t bytes = curr_kp ? o_kp + align16((size_t)c->tf_cap_kp * sizeof(vx_keypoint)) : o_kp;
+    VX_HIP(c, c->tf_host.ensure(bytes));
+    VX_HIP(c, hipMemcpyAsync(c->tf_host.p, c->tf_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) prof_collect(c);
+    const uint8_t* h = static_cast<const uint8_t*>(c->tf_host.p);
+    std::memcpy(out, h, sizeof *out);
+    c->tf_fetched = true;
+    if (n_kp) *n_kp = out->n_keypoints;
+    if (curr_kp) {
+        if (out->n_keypoints > cap_kp) return set_error(c, VX_ERR_CAPACITY, "need %d keypoints, cap %d", out->n_keypoints, cap_kp);
+        if (out->n_keypoints) std::memcpy(curr_kp, h + o_kp, (size_t)out->n_keypoints * sizeof(vx_keypoint));
+    }
+    return VX_OK;
+}
+
+int vx_track_frame_pairs(vx_ctx* c, int which, int32_t* pair_match, uint8_t* mask, int cap_pairs) {
+    if (!c) return VX_ERR_INVALID;
+    if (which != 0 && which != 1) return set_error(c, VX_ERR_INVALID, "vx_track_frame_pairs: path %d (0 or 1)", which);
+    if (!c->tf_valid || !c->tf_fetched) return set_error(c, VX_ERR_STATE, "no vx_track_frame_fetch before vx_track_frame_pairs");
+    const uint8_t* h = static_cast<const uint8_t*>(c->tf_host.p);
+    const vx_track_frame_result* r = reinterpret_cast<const vx_track_frame_result*>(h);
+    const int np = which ? r->ess.n_pairs : r->pnp.n_pairs;
+    if ((pair_match || mask) && np > cap_pairs) return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
+    size_t o_pm = align16(sizeof(vx_track_frame_result));
+    if (which) o_pm += align16((size_t)c->tf_pair_cap[0] * 4) + align16((size_t)c->tf_pair_cap[0]);
+    const size_t o_mask = o_pm + align16((size_t)c->tf_pair_cap[which] * 4);
+    if (pair_match && np) std::memcpy(pair_match, h + o_pm, (size_t)np * 4);
+    if (mask && np) std::memcpy(mask, h + o_mask, (size_t)np);
+    return VX_OK;
+}
+
+int vx_track_frame_matches(vx_ctx* c, int which, const vx_match** d_matches, const int32_t** d_n, int32_t* cap) {
+    if (!c) return VX_ERR_INVALID;
+    if (which != 0 && which != 1) return set_error(c, VX_ERR_INVALID, "vx_track_frame_matches: list %d (0 or 1)", which);
+    if (!c->tf_valid || c->tf_cap[which] <= 0) return set_error(c, VX_ERR_STATE, "vx_track_frame_async enqueued no match %d", which);
+    // list 1 may be list 0's rows under its own (gated) count
+    const bool shared = which == 1 && !c->tf_list1_own;
+    if (d_matches) *d_matches = c->tf_matches[shared ? 0 : which].as<vx_match>();
+    if (d_n) *d_n = c->tf_count.as<int32_t>() + 4 * which;
+    if (cap) *cap = c->tf_cap[which];
+    return VX_OK;
+}
+
+}  // extern "C"
+
+static_assert(sizeof(vx_track_frame_result) == 552 && offsetof(vx_track_frame_result, parallax) == 16 &&
+                  offsetof(vx_track_frame_result, pose) == 24 && offsetof(vx_track_frame_result, pnp_ran) == 80 &&
+                  offsetof(vx_track_frame_result, pnp) == 88 && offsetof(vx_track_frame_result, ess) == 264,
+              "vx_track_frame_result layout (python TRACK_FRAME_RESULT_DTYPE)");

@@ -173,7 +173,8 @@ static const char* kStageNames[vx::kStCount] = {
     "lm_depth",       "lm_triangulate", "lm_compact",  "pnp_hypotheses", "pnp_refine",
     "em_hypotheses",  "em_select",     "ba_iter",         "ba_prologue",
     "ba_window",      "track_pairs",   "kf_features",     "kf_matches",  "kf_commit",
-    "track_epairs",   "track_epose",   "init_sums",       "init_gate"};
+    "track_epairs",   "track_epose",   "init_sums",       "init_gate",
+    "frame_capture",  "track_gate",    "track_final"};
 
 extern "C" {
 
@@ -247,7 +248,7 @@ void vx_destroy(vx_ctx* c) {
     if (c->snap_map) vx_dmap_destroy(c->snap_map);
     vx::plan_pool_release(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto e : {c->order_event, c->tk_in_event, c->te_in_event, c->ig_in_event})
+    for (auto e : {c->order_event, c->tk_in_event, c->te_in_event, c->ig_in_event, c->fr_in_event})
         if (e) (void)hipEventDestroy(e);
 #ifndef VX_NO_RCCL
     if (c->comm) ncclCommDestroy(c->comm);

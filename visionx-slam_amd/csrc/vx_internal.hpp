@@ -74,6 +74,9 @@ enum Stage : int {
     kStTrackEPose,    // its T_cl * T_lw (k_track_epose)
     kStInitSums,      // InitWithFirstFrame's gray sum / sum of squares (k_init_sums)
     kStInitGate,      // its occupancy grid, meanStdDev and gates (k_init_gate)
+    kStFrameCapture,  // a slot's rows into a device-resident frame (k_frame_capture)
+    kStTrackGate,     // Track()'s PnP -> essential fallback decision (k_track_gate)
+    kStTrackFinal,    // its result head and packed block (k_track_final)
     kStCount
 };
 
@@ -185,6 +188,17 @@ struct GraphCache {
 
 struct vx_ba_plan;
 
+// a frame's features on the device (frame.hip): count[4] | vx_keypoint[cap] | uint8[cap * 32]
+struct vx_frame {
+    int device = 0;
+    int cap = 0;
+    vx::DevBuf block;
+    size_t off_kp = 16, off_desc = 0, bytes = 0;
+    int32_t* count() const { return block.as<int32_t>(); }
+    vx_keypoint* kp() const { return reinterpret_cast<vx_keypoint*>(block.as<uint8_t>() + off_kp); }
+    uint8_t* desc() const { return block.as<uint8_t>() + off_desc; }
+};
+
 struct vx_event {
     int device = 0;
     hipEvent_t ev = nullptr;
@@ -258,6 +272,21 @@ struct vx_ctx {
     vx::DevBuf ig_in;            // ... into one device block
     hipEvent_t ig_in_event = nullptr;  // (recorded after that upload)
     bool ig_valid = false;
+
+    // ---- device-resident frames (frame.hip): the pinned staging of vx_frame_extract_host_async (image
+    // rows) and vx_frame_upload_async (the frame block), and the pinned block vx_frame_fetch copies into
+    vx::PinnedBuf fr_in_host, fr_host;
+    hipEvent_t fr_in_event = nullptr;  // (recorded after the upload: the staging is reused once it has passed)
+
+    // ---- Tracking::Track() on the device (track_frame.hip): both match lists, the gate record, the
+    // packed result (device + pinned); the pair / RANSAC scratch is tk_* and te_*
+    vx::DevBuf tf_matches[2], tf_count, tf_gate, tf_out;  // tf_count: int32[8], list i's count at [4 * i]
+    vx::PinnedBuf tf_host;
+    int tf_cap[2] = {0, 0};      // match capacities of the enqueued call (0: that match was not enqueued)
+    int tf_pair_cap[2] = {0, 0}; // pair capacities of the two paths (size the packed block's pair arrays)
+    int tf_cap_kp = 0;           // keypoint rows the packed block holds
+    bool tf_list1_own = true;    // false: list 1 is list 0's rows under a gated count (last_kf == last)
+    bool tf_valid = false, tf_fetched = false;
 
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {
@@ -335,6 +364,12 @@ inline hipError_t launch(vx_ctx* c, int stage, F kernel, dim3 grid, dim3 block, 
 }
 
 int orb_prepare(vx_ctx* c, const vx_orb_params* p, int w, int h);
+
+// kNN-2 + ratio matching of device descriptor sets (match.hip) into a caller's list: `out` holds
+// q_cap vx_match rows, out_count one int32; c->partial is the only context buffer it uses.  Enqueued
+// on c->stream, nothing synchronised.  vx_match_* pass the context's own list (c->matches).
+int match_enqueue_to(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, const uint8_t* dt, const int* dnt,
+                     int nt_host, int q_cap, int t_cap, float ratio, vx_match* out, int* out_count);
 
 // PnP RANSAC on problems already in device memory (ransac.hip): k_pnp_hyp over (hmax, P) and
 // k_pnp_refine over P enqueued on c->stream, nothing synchronised.  Problem p owns correspondences

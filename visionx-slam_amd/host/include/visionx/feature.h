@@ -45,8 +45,14 @@ public:
     // Descriptors() end up exactly as Extract(frame) leaves them; frames of differing size or
     // channel count, or empty ones, are extracted one by one.
     void ExtractBatch(const std::vector<Frame::Ptr>& frames);
+    // Resident mode: vx_frame_extract_host_async into the frame's device handle (created on first use) on
+    // the context set by UseContext (nullptr: the calling thread's).  No synchronisation; Features() and
+    // Descriptors() are left untouched (FrameTracker::TrackResident fills Features(), Materialize both).
+    void UseContext(vx_ctx* ctx) { ctx_ = ctx; }
+    void ExtractResident(Frame& frame);
 
 private:
+    vx_ctx* ctx_ = nullptr;
     vx_orb_params params_;
     std::vector<vx_keypoint> kp_;
     std::vector<uint8_t> desc_;
@@ -60,6 +66,7 @@ public:
     };
     ORBMatcher() : ORBMatcher(Options()) {}
     explicit ORBMatcher(const Options& options);
+    const Options& options() const { return options_; }
     int Match(const Frame::Ptr& last, const Frame::Ptr& curr, std::vector<DMatch>& matches) override;
     // Extension: Match(last_i, curr_i, matches[i]) for up to VX_MAX_MATCH_PAIRS pairs in one launch
     // pair (vx_match_knn2_ratio_batch); returns the per-pair counts Match() would return.
@@ -163,6 +170,14 @@ private:
     std::vector<double> kf_out_, lm_out_;
     FlatMap flat_;  // the snapshot path's window, reused call after call
 };
+
+// Resident frames for features that came from elsewhere (a replay extractor): n float2 positions and n
+// 32-byte rows into the frame's device handle (created on first use), one copy, no synchronisation.
+void UploadResident(vx_ctx* ctx, Frame& frame, const float* xy, const uint8_t* desc, int n);
+// Fetches a resident frame's keypoints and descriptors into Features() (position, response; the
+// landmark links of features already there are kept) and Descriptors(): one copy, one synchronisation.
+// descriptors = false: the keypoints only (Descriptors() untouched).
+void Materialize(vx_ctx* ctx, Frame& frame, bool descriptors = true);
 
 namespace vxhost {
 vx_ctx* ThreadContext();  // the calling thread's context (device $VX_DEVICE, default 0)

@@ -11,7 +11,25 @@
 
 #include "visionx/types.h"
 
+struct vx_frame;  // include/vx_slam.h
+
 namespace visionx {
+
+// Owner of a vx_frame: the frame's keypoints, descriptors and count on the device for as long as the
+// Frame (or anything else holding the pointer) lives.  Destroyed with vx_frame_destroy (feature.cpp).
+class ResidentFrame {
+public:
+    explicit ResidentFrame(vx_frame* handle, int cap) : handle_(handle), cap_(cap) {}
+    ~ResidentFrame();
+    ResidentFrame(const ResidentFrame&) = delete;
+    ResidentFrame& operator=(const ResidentFrame&) = delete;
+    vx_frame* handle() const { return handle_; }
+    int capacity() const { return cap_; }
+
+private:
+    vx_frame* handle_;
+    int cap_;
+};
 
 class Camera {  // camera.h:8-37 (only the getters are on the hot path, camera.h:29-32)
 public:
@@ -60,6 +78,9 @@ public:
     DescriptorMat& Descriptors() { return descriptors_; }
     const DescriptorMat& Descriptors() const { return descriptors_; }
     std::shared_ptr<Camera> GetCamera() const { return camera_; }
+    // resident mode (opt-in; empty by default): the device copy of this frame's features
+    const std::shared_ptr<ResidentFrame>& Resident() const { return resident_; }
+    void SetResident(std::shared_ptr<ResidentFrame> r) { resident_ = std::move(r); }
 
 private:
     uint64_t id_ = 0;
@@ -71,6 +92,7 @@ private:
     DepthImage depth_;
     std::vector<Feature> features_;
     DescriptorMat descriptors_;
+    std::shared_ptr<ResidentFrame> resident_;
 };
 
 class Landmark {  // landmark.h:12-68

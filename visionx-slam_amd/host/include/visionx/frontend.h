@@ -74,6 +74,23 @@ public:
 
     void ProcessFrame(Frame::Ptr frame);
 
+    // Resident frames (opt-in, before the first frame): every frame's keypoints and
+    // descriptors stay on the device for as long as the Frame lives, and ProcessFrame calls no
+    // FeatureMatcher::Match at all:
+    //   extraction   ORBExtractor::ExtractResident (no synchronisation); any other extractor must leave a
+    //                resident handle on the frame itself (UploadResident) in its Extract
+    //   InitWithFirstFrame   one vx_frame_fetch of the keypoints, then the host-input gate (the image is
+    //                on the host anyway)
+    //   InitWithSecondFrame  FrameTracker::EstimateInitialPoseResident; the two CreateKeyFrame calls reuse
+    //                its match list
+    //   Track        FrameTracker::TrackResident: one enqueue, one synchronisation whichever path it takes
+    //   CreateKeyFrame  the track's own match list (KeyFrameLandmarks::UseTrackLists)
+    // Throws std::logic_error after the first frame, and std::invalid_argument unless the matcher is an
+    // ORBMatcher, whose nn_ratio is then the one ratio used everywhere.  Features() are filled as in the
+    // default mode; Descriptors() stay empty (Materialize fetches them on demand).
+    void UseResidentFrames(bool on);
+    bool ResidentFrames() const { return resident_; }
+
     State GetState() const { return state_; }
 
     // read-only views of the private members (tracking.h:105-122) and of the last calls
@@ -121,6 +138,7 @@ private:
     std::unique_ptr<LocalBA> local_ba_;
     vx_init_gate_result last_gate_{};
     std::vector<float> xy_;
+    bool resident_ = false;
 };
 
 }  // namespace visionx

@@ -22,6 +22,8 @@
 
 namespace visionx {
 
+class FrameTracker;  // tracking.h
+
 class KeyFrameLandmarks {
 public:
     struct Options {
@@ -44,6 +46,13 @@ public:
     // time.  curr arrives without links (tracking.cpp:577); last_frame may be null (the first frame
     // of InitWithSecondFrame: no triangulation).  Returns the next landmark_id_.
     uint64_t CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr curr_frame);
+    // Resident mode: with a tracker attached, CreateKeyFrame on frames that hold resident handles
+    // (frame.h) is vx_dmap_create_keyframe_frame on the current frame's device positions and the
+    // match list the tracker's last resident call holds for these two frames (checked by frame id);
+    // only when it holds none are the two frames matched, on the device.  matcher_->Match is not
+    // called; the depth image is uploaded, one copy per keyframe; the records and the host mirrors
+    // are handled exactly as in the host-input form.  nullptr (default): the host-input form.
+    void UseTrackLists(const FrameTracker* tracker) { tracks_ = tracker; }
     const std::vector<vx_keyframe_landmark>& LastRecords() const { return rec_; }
 
     uint64_t landmark_id_ = 0;  // Tracking::landmark_id_ (tracking.h): next landmark id
@@ -58,6 +67,7 @@ private:
     std::vector<vx_match> m_;
     std::shared_ptr<DeviceMap> dmap_;
     std::vector<vx_keyframe_landmark> rec_;
+    const FrameTracker* tracks_ = nullptr;
 };
 
 }  // namespace visionx

@@ -44,6 +44,7 @@ public:
     const vx_track_result& LastResult() const { return last_; }  // every count of the last call
 
 private:
+    friend class FrameTracker;  // TrackResident sets last_ / last_inliers_ / last_parallax_ as TrackWithPnP does
     DeviceMap::Ptr map_;
     Options options_;
     vx_track_result last_{};
@@ -93,6 +94,7 @@ public:
     const vx_track_essential_result& LastResult() const { return last_; }  // every count of the last call
 
 private:
+    friend class FrameTracker;  // TrackResident sets last_ / last_inliers_ / last_parallax_ as TrackLastFrame does
     bool Run(const Frame::Ptr& last, const Frame::Ptr& current, const double* pose_last7);
     vx_ctx* ctx_;
     Options options_;
@@ -117,6 +119,28 @@ public:
     // last_keyframe may be null (no PnP attempt, :269); last_frame null -> false (:282-285)
     bool Track(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current);
 
+    // Track() over resident frames (frame.h: Frame::Resident(), filled by ORBExtractor::ExtractResident or
+    // UploadResident): ONE vx_track_frame_async and one fetch whichever path sets the pose, the PnP ->
+    // TrackLastFrame decision taken on the device (csrc/track_frame.hip).  Returns what Track returns
+    // and sets the pose, UsedFallback(), LastInliers() and LastParallax() as Track sets them; the fetch
+    // also fills current->Features() (position, response) from the keypoint rows it brings down.
+    // Descriptors() stays empty (Materialize fetches them on demand).  Every frame given must have a
+    // resident handle (std::invalid_argument otherwise).
+    bool TrackResident(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current);
+    // EssentialTracker::EstimateInitialPose (tracking.cpp:207-245) over resident frames: the same call
+    // with no last keyframe and T_lw = identity, then the parallax gate; sets Essential()'s LastInliers /
+    // LastParallax as EstimateInitialPose does and fills current->Features().
+    bool EstimateInitialPoseResident(const Frame::Ptr& init, const Frame::Ptr& current);
+    // The device match list the last resident call holds for Match(query, train), by frame ids
+    // (tracking.cpp:340 and :863, and :208 and :863, match the same two frames): false when it holds none.
+    bool MatchList(uint64_t query_id, uint64_t train_id, const vx_match** d_matches, const int32_t** d_n, int32_t* cap) const;
+    // Resident calls use ONE ratio for both matches (the matcher's nn_ratio, set by Tracking::UseResidentFrames);
+    // TrackResident throws when the two component trackers' ratios differ.
+    void SetRatio(float nn_ratio);
+    float Ratio() const;
+    const DeviceMap::Ptr& ResidentMap() const;
+    const vx_track_frame_result& LastResidentResult() const { return resident_; }
+
     bool UsedFallback() const { return used_fallback_; }     // the last Track() ran TrackLastFrame
     int LastInliers() const { return used_fallback_ ? essential_.LastInliers() : pnp_.LastInliers(); }
     double LastParallax() const { return used_fallback_ ? essential_.LastParallax() : pnp_.LastParallax(); }
@@ -127,6 +151,13 @@ private:
     PnPTracker pnp_;
     EssentialTracker essential_;
     bool used_fallback_ = false;
+    void RunResident(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current,
+                     bool identity_last);
+    vx_track_frame_result resident_{};
+    std::vector<vx_keypoint> kp_;
+    // (query frame id, train frame id) of the two device match lists of the last resident call
+    uint64_t list_ids_[2][2] = {{0, 0}, {0, 0}};
+    bool list_valid_[2] = {false, false};
 };
 
 }  // namespace visionx

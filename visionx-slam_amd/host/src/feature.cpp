@@ -101,6 +101,55 @@ void ORBExtractor::Extract(Frame& frame) {
     frame.Descriptors() = std::move(d);
 }
 
+ResidentFrame::~ResidentFrame() { vx_frame_destroy(handle_); }
+
+// the frame's device handle, created on first use with room for `cap` rows
+static vx_frame* ResidentHandle(vx_ctx* c, Frame& frame, int cap) {
+    if (!frame.Resident() || frame.Resident()->capacity() < cap) {
+        vx_frame* h = nullptr;
+        check(c, vx_frame_create(c, cap, &h), "vx_frame_create");
+        frame.SetResident(std::make_shared<ResidentFrame>(h, cap));
+    }
+    return frame.Resident()->handle();
+}
+
+void ORBExtractor::ExtractResident(Frame& frame) {
+    const ImageU8& img = frame.Image();
+    vx_ctx* c = ctx_ ? ctx_ : vxhost::ThreadContext();
+    vx_frame* h = ResidentHandle(c, frame, 2 * params_.n_features + 256);
+    if (img.empty()) {  // detectAndCompute returns early on an empty image: an empty frame
+        check(c, vx_frame_upload_async(c, h, nullptr, nullptr, 0), "vx_frame_upload_async");
+        return;
+    }
+    check(c, vx_frame_extract_host_async(c, h, &params_, img.ptr(), img.cols, img.rows, img.channels, (int64_t)img.step()),
+          "vx_frame_extract_host_async");
+}
+
+void UploadResident(vx_ctx* c, Frame& frame, const float* xy, const uint8_t* desc, int n) {
+    check(c, vx_frame_upload_async(c, ResidentHandle(c, frame, std::max(n, 1)), xy, desc, n), "vx_frame_upload_async");
+}
+
+void Materialize(vx_ctx* c, Frame& frame, bool descriptors) {
+    if (!frame.Resident()) throw std::invalid_argument("Materialize: the frame has no resident handle");
+    const int cap = frame.Resident()->capacity();
+    std::vector<vx_keypoint> kp((size_t)cap);
+    DescriptorMat d;
+    if (descriptors) d.data.resize((size_t)cap * 32);
+    int n = 0;
+    check(c, vx_frame_fetch(c, frame.Resident()->handle(), kp.data(), descriptors ? d.data.data() : nullptr, cap, &n),
+          "vx_frame_fetch");
+    auto& features = frame.Features();
+    features.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        features[i].position = Vec2d(kp[i].x, kp[i].y);
+        features[i].response = kp[i].response;
+    }
+    if (!descriptors) return;
+    d.rows = n;
+    d.data.resize((size_t)n * 32);
+    frame.Descriptors() = std::move(d);
+}
+
 void ORBExtractor::ExtractBatch(const std::vector<Frame::Ptr>& frames) {
     if (frames.empty()) return;
     const ImageU8& i0 = frames[0]->Image();

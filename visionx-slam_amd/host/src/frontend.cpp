@@ -59,12 +59,34 @@ Tracking::Tracking(const Options& options, std::shared_ptr<FeatureExtractor> ext
     }
 }
 
+void Tracking::UseResidentFrames(bool on) {
+    if (current_frame_) throw std::logic_error("Tracking::UseResidentFrames: only before the first frame");
+    if (on) {
+        const auto* orb = dynamic_cast<const ORBMatcher*>(matcher_.get());
+        if (!orb) throw std::invalid_argument("Tracking::UseResidentFrames: the matcher is not an ORBMatcher");
+        tracker_.SetRatio(orb->options().nn_ratio);
+        if (auto* ex = dynamic_cast<ORBExtractor*>(extractor_.get())) ex->UseContext(dmap_->context());
+    }
+    keyframes_.UseTrackLists(on ? &tracker_ : nullptr);
+    resident_ = on;
+}
+
 // ================= the entry point (tracking.cpp:39-89) =================
 
 void Tracking::ProcessFrame(Frame::Ptr frame) {
     current_frame_ = frame;
 
-    extractor_->Extract(*current_frame_);
+    if (resident_) {
+        if (auto* orb = dynamic_cast<ORBExtractor*>(extractor_.get())) {
+            orb->ExtractResident(*current_frame_);
+        } else {
+            extractor_->Extract(*current_frame_);
+            if (!current_frame_->Resident())
+                throw std::runtime_error("Tracking: resident frames, but the extractor left no resident handle on the frame");
+        }
+    } else {
+        extractor_->Extract(*current_frame_);
+    }
     bool just_initialized = false;
 
     if (state_ == State::INIT) {
@@ -107,6 +129,9 @@ void Tracking::ProcessFrame(Frame::Ptr frame) {
 
 // tracking.cpp:177-204: the feature count, CheckFeatureDistribution and CheckImageQuality as one call
 bool Tracking::InitWithFirstFrame() {
+    // resident frames: the gate stays the host-input one (the image is on the host anyway), after one
+    // fetch of the keypoints
+    if (resident_) Materialize(dmap_->context(), *current_frame_, false);
     const auto& feats = current_frame_->Features();
     const ImageU8& image = current_frame_->Image();
     last_gate_ = vx_init_gate_result{};
@@ -146,7 +171,9 @@ bool Tracking::InitWithFirstFrame() {
 // tracking.cpp:206-263
 bool Tracking::InitWithSecondFrame() {
     EssentialTracker& essential = tracker_.Essential();
-    if (!essential.EstimateInitialPose(init_frame_, current_frame_)) return false;  // :207-245
+    if (!(resident_ ? tracker_.EstimateInitialPoseResident(init_frame_, current_frame_)
+                    : essential.EstimateInitialPose(init_frame_, current_frame_)))
+        return false;  // :207-245
     keyframes_.CreateKeyFrame(nullptr, init_frame_);          // init's depth landmarks, its insertion (:248, :255)
     keyframes_.CreateKeyFrame(init_frame_, current_frame_);   // current's depth landmarks, triangulation (:249-256)
     last_keyframe_ = current_frame_;
@@ -158,7 +185,9 @@ bool Tracking::InitWithSecondFrame() {
 // ================= tracking (tracking.cpp:267-279) =================
 
 bool Tracking::Track() {
-    if (!tracker_.Track(last_keyframe_, last_frame_, current_frame_)) return false;
+    if (!(resident_ ? tracker_.TrackResident(last_keyframe_, last_frame_, current_frame_)
+                    : tracker_.Track(last_keyframe_, last_frame_, current_frame_)))
+        return false;
     last_parallax_ = tracker_.LastParallax();  // :325 / :449
     last_inliers_ = tracker_.LastInliers();    // :324 / :450
     return true;

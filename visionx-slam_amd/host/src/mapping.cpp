@@ -1,5 +1,6 @@
 // mapping.cpp — KeyFrameLandmarks over vx_depth_landmarks / vx_triangulate (see mapping.h).
 #include "visionx/mapping.h"
+#include "visionx/tracking.h"
 
 #include "visionx/device_map.h"
 
@@ -126,17 +127,7 @@ uint64_t KeyFrameLandmarks::CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr cur
     if (!map_ || !curr_frame) return landmark_id_;
     const auto cam = curr_frame->GetCamera();
     if (!cam) throw std::runtime_error("KeyFrameLandmarks::CreateKeyFrame: the frame has no camera");
-    std::vector<DMatch> matches;
-    if (last_frame) matcher_->Match(last_frame, curr_frame, matches);
     auto& f2 = curr_frame->Features();
-    const int n = (int)f2.size(), nm = (int)matches.size();
-    uv_.resize(2 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        uv_[2 * i] = f2[i].position.x;
-        uv_[2 * i + 1] = f2[i].position.y;
-    }
-    m_.resize(nm);
-    for (int k = 0; k < nm; ++k) m_[k] = vx_match{matches[k].queryIdx, matches[k].trainIdx, matches[k].distance};
     const double intr[4] = {cam->fx(), cam->fy(), cam->cx(), cam->cy()};
     double T[7];
     pose7(curr_frame->Pose(), T);
@@ -145,11 +136,42 @@ uint64_t KeyFrameLandmarks::CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr cur
     dmap_->Flush();  // queued edits first: the call reads the resident map
     vx_ctx* c = dmap_->context();
     vx_keyframe_result res{};
-    check(c, vx_dmap_create_keyframe_host(c, dmap_->handle(), curr_frame->Id(), T, intr, uv_.data(), n,
-                                          last_frame ? 1 : 0, last_frame ? last_frame->Id() : 0, m_.data(), nm,
-                                          depth.empty() ? nullptr : depth.ptr(), depth.type, depth.rows, depth.cols,
-                                          (int64_t)depth.step, landmark_id_, &o, &res),
-          "vx_dmap_create_keyframe_host");
+    if (tracks_ && curr_frame->Resident() && (!last_frame || last_frame->Resident())) {
+        // resident frames: the track's own match list (tracking.cpp:340 / :208 matched these two frames
+        // a moment ago), or a device match when it holds none; no host matcher either way
+        const vx_match* dm = nullptr;
+        const int32_t* dn = nullptr;
+        int32_t mcap = 0;
+        if (last_frame && !tracks_->MatchList(last_frame->Id(), curr_frame->Id(), &dm, &dn, &mcap)) {
+            const uint8_t *qd, *td;
+            const int32_t *qn, *tn;
+            int32_t qc, tc;
+            check(c, vx_frame_device(last_frame->Resident()->handle(), nullptr, nullptr, &qd, &qn, &qc), "vx_frame_device");
+            check(c, vx_frame_device(curr_frame->Resident()->handle(), nullptr, nullptr, &td, &tn, &tc), "vx_frame_device");
+            check(c, vx_match_device_async(c, qd, qn, qc, td, tn, tc, tracks_->Ratio()), "vx_match_device_async");
+        }
+        check(c, vx_dmap_create_keyframe_frame(c, dmap_->handle(), curr_frame->Id(), T, intr, curr_frame->Resident()->handle(),
+                                               last_frame ? 1 : 0, last_frame ? last_frame->Id() : 0, dm, dn, mcap,
+                                               depth.empty() ? nullptr : depth.ptr(), depth.type, depth.rows, depth.cols,
+                                               (int64_t)depth.step, landmark_id_, &o, &res),
+              "vx_dmap_create_keyframe_frame");
+    } else {
+        std::vector<DMatch> matches;
+        if (last_frame) matcher_->Match(last_frame, curr_frame, matches);
+        const int n = (int)f2.size(), nm = (int)matches.size();
+        uv_.resize(2 * (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            uv_[2 * i] = f2[i].position.x;
+            uv_[2 * i + 1] = f2[i].position.y;
+        }
+        m_.resize(nm);
+        for (int k = 0; k < nm; ++k) m_[k] = vx_match{matches[k].queryIdx, matches[k].trainIdx, matches[k].distance};
+        check(c, vx_dmap_create_keyframe_host(c, dmap_->handle(), curr_frame->Id(), T, intr, uv_.data(), n,
+                                              last_frame ? 1 : 0, last_frame ? last_frame->Id() : 0, m_.data(), nm,
+                                              depth.empty() ? nullptr : depth.ptr(), depth.type, depth.rows, depth.cols,
+                                              (int64_t)depth.step, landmark_id_, &o, &res),
+              "vx_dmap_create_keyframe_host");
+    }
     int n_rec = 0;
     rec_.resize((size_t)res.n_depth + (size_t)res.n_triangulated);
     check(c, vx_dmap_create_results(dmap_->handle(), (int)rec_.size(), rec_.data(), &n_rec), "vx_dmap_create_results");

@@ -137,4 +137,113 @@ bool FrameTracker::Track(const Frame::Ptr& last_keyframe, const Frame::Ptr& last
     return essential_.TrackLastFrame(last_frame, current);                        // (:278)
 }
 
+static void SetPose7(const Frame::Ptr& f, const double* p) {
+    SE3d T;
+    T.qx = p[0]; T.qy = p[1]; T.qz = p[2]; T.qw = p[3];
+    T.tx = p[4]; T.ty = p[5]; T.tz = p[6];
+    f->SetPose(T);
+}
+
+void FrameTracker::SetRatio(float nn_ratio) { pnp_.options_.nn_ratio = essential_.options_.nn_ratio = nn_ratio; }
+float FrameTracker::Ratio() const { return pnp_.options_.nn_ratio; }
+const DeviceMap::Ptr& FrameTracker::ResidentMap() const { return pnp_.map_; }
+
+bool FrameTracker::MatchList(uint64_t query_id, uint64_t train_id, const vx_match** d_matches, const int32_t** d_n,
+                             int32_t* cap) const {
+    for (int which = 0; which < 2; ++which)
+        if (list_valid_[which] && list_ids_[which][0] == query_id && list_ids_[which][1] == train_id)
+            return vx_track_frame_matches(pnp_.map_->context(), which, d_matches, d_n, cap) == VX_OK;
+    return false;
+}
+
+// one vx_track_frame_async + fetch; fills resident_, current->Features() and the list ids
+void FrameTracker::RunResident(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current,
+                               bool identity_last) {
+    for (const Frame::Ptr& f : {last_keyframe, last_frame, current})
+        if (f && !f->Resident()) throw std::invalid_argument("FrameTracker: a frame without a resident handle");
+    if (pnp_.options_.nn_ratio != essential_.options_.nn_ratio)
+        throw std::invalid_argument("FrameTracker: resident calls take one nn_ratio for both matches (SetRatio)");
+    const auto cam = current->GetCamera();
+    const double intr[4] = {cam->fx(), cam->fy(), cam->cx(), cam->cy()};
+    DeviceMap::Ptr& map = pnp_.map_;
+    map->Flush();
+    vx_track_options po;
+    vx_track_default_options(&po);
+    po.min_matches = pnp_.options_.min_matches;
+    po.min_inliers = pnp_.options_.min_inliers;
+    po.pnp.reproj_error = pnp_.options_.max_reproj_error;
+    vx_track_essential_options eo;
+    vx_track_essential_default_options(&eo);
+    eo.min_matches = essential_.options_.min_matches;
+    eo.min_inliers = essential_.options_.min_inliers;
+    double pose_last[7] = {0, 0, 0, 1, 0, 0, 0};
+    if (last_frame && !identity_last) {
+        const SE3d L = last_frame->Pose();
+        const double p[7] = {L.qx, L.qy, L.qz, L.qw, L.tx, L.ty, L.tz};
+        for (int i = 0; i < 7; ++i) pose_last[i] = p[i];
+    }
+    list_valid_[0] = list_valid_[1] = false;
+    vx_ctx* c = map->context();
+    int rc = vx_track_frame_async(c, map->handle(), last_keyframe ? last_keyframe->Id() : 0,
+                                  last_keyframe ? last_keyframe->Resident()->handle() : nullptr,
+                                  last_frame ? last_frame->Resident()->handle() : nullptr, current->Resident()->handle(),
+                                  pnp_.options_.nn_ratio, identity_last ? nullptr : pose_last, intr, &po, &eo);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_frame_async: ") + vx_last_error(c));
+    kp_.resize((size_t)current->Resident()->capacity());
+    int n = 0;
+    rc = vx_track_frame_fetch(c, &resident_, kp_.data(), (int)kp_.size(), &n);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_frame_fetch: ") + vx_last_error(c));
+    auto& feats = current->Features();  // what ORBExtractor::Extract leaves there (orb_extractor.cpp:19-24)
+    feats.assign((size_t)n, Feature());
+    for (int i = 0; i < n; ++i) {
+        feats[i].position = Vec2d(kp_[i].x, kp_[i].y);
+        feats[i].response = kp_[i].response;
+    }
+    if (last_keyframe) {
+        list_ids_[0][0] = last_keyframe->Id(), list_ids_[0][1] = current->Id();
+        list_valid_[0] = true;
+    }
+    if (last_frame && resident_.ess_ran) {  // (a closed gate leaves list 1 empty)
+        list_ids_[1][0] = last_frame->Id(), list_ids_[1][1] = current->Id();
+        list_valid_[1] = true;
+    }
+    if (resident_.pnp_ran) pnp_.last_ = resident_.pnp;
+    if (resident_.ess_ran) essential_.last_ = resident_.ess;
+}
+
+bool FrameTracker::TrackResident(const Frame::Ptr& last_keyframe, const Frame::Ptr& last_frame, const Frame::Ptr& current) {
+    used_fallback_ = false;
+    if (!current) return false;  // tracking.cpp:333-336, :282-285
+    if (!current->GetCamera() || (!last_keyframe && !last_frame)) {
+        used_fallback_ = true;  // Track() gets to TrackLastFrame, which returns false (:282-285, :516)
+        return false;
+    }
+    RunResident(last_keyframe, last_frame, current, false);
+    if (resident_.path == VX_TRACK_PATH_PNP) {  // (:443-450)
+        SetPose7(current, resident_.pose);
+        pnp_.last_parallax_ = resident_.parallax;
+        pnp_.last_inliers_ = resident_.n_inliers;
+        return true;
+    }
+    used_fallback_ = true;
+    if (resident_.path != VX_TRACK_PATH_ESSENTIAL) return false;
+    SetPose7(current, resident_.pose);  // (:539-541, :324-325)
+    essential_.last_inliers_ = resident_.n_inliers;
+    essential_.last_parallax_ = resident_.parallax;
+    return true;
+}
+
+bool FrameTracker::EstimateInitialPoseResident(const Frame::Ptr& init, const Frame::Ptr& current) {
+    if (!init || !current || !current->GetCamera()) return false;
+    RunResident(nullptr, init, current, true);  // T_lw = identity (:200)
+    if (resident_.path != VX_TRACK_PATH_ESSENTIAL) return false;
+    SetPose7(current, resident_.pose);                        // (:232 -> :541, before the parallax gate)
+    const float parallax = (float)resident_.parallax;         // (:240)
+    const float min_parallax = 1.0f * M_PI / 180.0f;          // (:241)
+    if (parallax < min_parallax) return false;                // (:242)
+    essential_.last_parallax_ = parallax;                     // (:259-260: the float, widened)
+    essential_.last_inliers_ = resident_.n_inliers;
+    return true;
+}
+
 }  // namespace visionx

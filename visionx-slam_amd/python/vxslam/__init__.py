@@ -104,6 +104,10 @@ EXPORTS = [
     "vx_track_essential_default_options", "vx_track_essential_async", "vx_track_essential_host_async",
     "vx_track_essential_fetch",
     "vx_init_gate_default_options", "vx_init_gate_async", "vx_init_gate_host_async", "vx_init_gate_fetch",
+    "vx_frame_create", "vx_frame_destroy", "vx_frame_capture_async", "vx_frame_extract_host_async",
+    "vx_frame_upload_async", "vx_frame_device", "vx_frame_fetch", "vx_frame_fetch_ex",
+    "vx_track_frame_async", "vx_track_frame_fetch", "vx_track_frame_pairs", "vx_track_frame_matches",
+    "vx_dmap_create_keyframe_frame",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -208,6 +212,24 @@ def lib():
         L.vx_init_gate_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                               C.c_int64, C.c_int, C.c_void_p]
         L.vx_init_gate_fetch.argtypes = [C.c_void_p, C.c_void_p]
+        L.vx_frame_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.vx_frame_destroy.argtypes = [C.c_void_p]
+        L.vx_frame_destroy.restype = None
+        L.vx_frame_capture_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.vx_frame_extract_host_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int64]
+        L.vx_frame_upload_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_frame_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+        L.vx_frame_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.vx_frame_fetch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]
+        L.vx_track_frame_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vx_track_frame_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.vx_track_frame_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_track_frame_matches.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_int32)]
         L.vx_cull_default_options.restype = None
         L.vx_cull_default_options.argtypes = [C.c_void_p]
         L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -330,6 +352,21 @@ def track_essential_options(min_matches=None, min_inliers=None, max_iterations=N
         if v is not None:
             o["ess"][k] = v
     return o
+
+
+# vx_track_frame_result (include/vx_slam.h; layout pinned in csrc/track_frame.hip)
+TRACK_FRAME_RESULT_DTYPE = np.dtype([("path", "<i4"), ("status", "<i4"), ("n_inliers", "<i4"), ("n_keypoints", "<i4"),
+                                     ("parallax", "<f8"), ("pose", "<f8", 7), ("pnp_ran", "<i4"), ("ess_ran", "<i4"),
+                                     ("pnp", TRACK_RESULT_DTYPE), ("ess", TRACK_ESS_RESULT_DTYPE)])
+TRACK_PATH_NONE, TRACK_PATH_PNP, TRACK_PATH_ESSENTIAL = range(3)
+
+
+def track_frame_options(min_matches=None, min_inliers=None, pnp=None, ess=None):
+    """(TRACK_OPTIONS_DTYPE, TRACK_ESS_OPTIONS_DTYPE) for Context.track_frame_async: Tracking::Options'
+    two gates (tracking.h:27-28) on both paths; pnp / ess: dicts of track_options /
+    track_essential_options keywords for the rest."""
+    return (track_options(min_matches, min_inliers, **(pnp or {})),
+            track_essential_options(min_matches, min_inliers, **(ess or {})))
 
 
 # vx_init_gate_options / vx_init_gate_result (include/vx_slam.h; sizes pinned in csrc/init_gate.hip)
@@ -730,6 +767,49 @@ class Context:
         n = int(out[0]["n_pairs"])
         return out[0], pm[:n].copy(), mask[:n].copy()
 
+    def track_frame_async(self, dmap, last_kf_id, last_kf, last, curr, intr, opts=None, ratio: float = 0.8,
+                          pose_last=None):
+        """Tracking::Track (tracking.cpp:267-279) over Frame handles in one enqueue: PnP against last_kf
+        (a Frame holding keyframe last_kf_id's features; None: straight to the fallback), and, decided
+        on the device, the essential fallback against `last` (None: the fallback fails).  opts: a
+        track_frame_options() pair.  Nothing synchronises; track_frame_fetch() completes it."""
+        po, eo = track_frame_options() if opts is None else opts
+        po = np.ascontiguousarray(po, TRACK_OPTIONS_DTYPE)
+        eo = np.ascontiguousarray(eo, TRACK_ESS_OPTIONS_DTYPE)
+        intr = np.ascontiguousarray(intr, np.float64)
+        assert intr.size == 4
+        pose = None if pose_last is None else np.ascontiguousarray(pose_last, np.float64)
+        assert pose is None or pose.size == 7
+        h = lambda f: None if f is None else f.handle
+        self._check(lib().vx_track_frame_async(self._h, None if dmap is None else dmap.handle, int(last_kf_id),
+                                               h(last_kf), h(last), h(curr), ratio,
+                                               None if pose is None else _p(pose), _p(intr), _p(po), _p(eo)))
+
+    def track_frame_fetch(self, keypoints: bool = True, cap: int = 8192):
+        """The last track_frame_async in one copy and one synchronisation: a dict of `result`
+        (TRACK_FRAME_RESULT_DTYPE), `pnp` and `ess` ((pair_match, mask) of each path) and `keypoints`
+        (the current frame's KEYPOINT_DTYPE rows; None with keypoints=False)."""
+        out = np.zeros(1, TRACK_FRAME_RESULT_DTYPE)
+        kp = np.zeros(max(cap, 1), KEYPOINT_DTYPE) if keypoints else None
+        n = C.c_int(0)
+        self._check(lib().vx_track_frame_fetch(self._h, _p(out), None if kp is None else _p(kp), cap, C.byref(n)))
+        pairs = []
+        for which, rec in ((0, out[0]["pnp"]), (1, out[0]["ess"])):
+            k = int(rec["n_pairs"])
+            pm, mask = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.uint8)
+            self._check(lib().vx_track_frame_pairs(self._h, which, _p(pm), _p(mask), k))
+            pairs.append((pm[:k].copy(), mask[:k].copy()))
+        return {"result": out[0], "pnp": pairs[0], "ess": pairs[1],
+                "keypoints": None if kp is None else kp[:n.value].copy()}
+
+    def track_frame_matches(self, which: int):
+        """(device pointer of MATCH_DTYPE rows, device pointer of the int32 count, capacity) of the PnP
+        match (0) or the fallback match (1) of the last track_frame_async: what track_*_async and
+        DMap.create_keyframe take as `matches`."""
+        d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._check(lib().vx_track_frame_matches(self._h, int(which), C.byref(d), C.byref(n), C.byref(cap)))
+        return d.value, n.value, cap.value
+
     def init_gate_async(self, d_img_ptr: int, w: int, h: int, channels: int, row_stride: int, feats, opts=None,
                         cap_feat: int | None = None):
         """Tracking::InitWithFirstFrame's gates (tracking.cpp:177-197) on a device image.  feats: an
@@ -1023,6 +1103,79 @@ class Context:
         cnt = (C.c_int64 * n)()
         self._check(lib().vx_prof_read(self._h, ms, cnt, 1 if reset else 0))
         return {lib().vx_prof_name(i).decode(): (ms[i], cnt[i]) for i in range(n)}
+
+
+class Frame:
+    """A frame's keypoints, descriptors and count on the device for as long as the object lives
+    (vx_frame): what Context.track_frame_async, match_device_async, track_*_async and
+    DMap.create_keyframe read, without a slot that the next extraction overwrites."""
+
+    def __init__(self, ctx: Context, cap: int):
+        self._h = C.c_void_p()
+        self.cap = int(cap)
+        ctx._check(lib().vx_frame_create(ctx._h, int(cap), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def capture(self, ctx: Context, slot: int):
+        """an extraction slot of ctx -> this frame (one launch on ctx's stream, no synchronisation)"""
+        ctx._check(lib().vx_frame_capture_async(ctx._h, int(slot), self._h))
+        return self
+
+    def extract_host(self, ctx: Context, img: np.ndarray, params: OrbParams | None = None):
+        """ORBExtractor::Extract of a host image into this frame (upload, extraction, capture; no
+        synchronisation): orb_extract's keypoints and descriptors, byte for byte"""
+        img = np.ascontiguousarray(img)
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        params = params or default_orb_params()
+        ctx._check(lib().vx_frame_extract_host_async(ctx._h, self._h, C.byref(params), _p(img), w, h, ch,
+                                                     C.c_int64(img.strides[0])))
+        return self
+
+    def upload(self, ctx: Context, xy, desc):
+        """host float2 positions + 32-byte rows -> this frame in one copy (the other keypoint fields 0)"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(xy) == len(desc)
+        ctx._check(lib().vx_frame_upload_async(ctx._h, self._h, _p(xy), _p(desc), len(xy)))
+        return self
+
+    def device(self):
+        """dict of the device pointers the device-input forms take: xy (first x), stride (20), desc,
+        count, cap; `rows` = the (xy, stride, count) triple of track_*_async, `desc_rows` = the
+        (desc, count, cap) triple of match_device_async"""
+        xy, st, d, n, cap = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        rc = lib().vx_frame_device(self._h, C.byref(xy), C.byref(st), C.byref(d), C.byref(n), C.byref(cap))
+        if rc != VX_OK:
+            raise VxError(rc, "vx_frame_device: no frame")
+        return {"xy": xy.value, "stride": st.value, "desc": d.value, "count": n.value, "cap": cap.value,
+                "rows": (xy.value, st.value, n.value), "desc_rows": (d.value, n.value, cap.value)}
+
+    def fetch(self, ctx: Context, descriptors: bool = True, cap: int | None = None, overflow: bool = False):
+        """(keypoints, descriptors) — descriptors None with descriptors=False — in one copy and one
+        synchronisation of ctx; overflow=True appends the frame's overflow flag"""
+        cap = self.cap if cap is None else cap
+        kp = np.zeros(max(cap, 1), KEYPOINT_DTYPE)
+        desc = np.zeros((max(cap, 1), 32), np.uint8) if descriptors else None
+        n, ov = C.c_int(0), C.c_int(0)
+        ctx._check(lib().vx_frame_fetch_ex(ctx._h, self._h, _p(kp), None if desc is None else _p(desc), cap,
+                                           C.byref(n), C.byref(ov)))
+        out = (kp[:n.value].copy(), None if desc is None else desc[:n.value].copy())
+        return out + (ov.value,) if overflow else out
+
+    def close(self):
+        if self._h:
+            lib().vx_frame_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BAPlan:

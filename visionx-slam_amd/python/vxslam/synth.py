@@ -545,6 +545,48 @@ def make_last_frame_scene(seed: int, n_feat: int = 300, *, wrong_frac: float = 0
             "R_cw": tv["R"] @ quat_to_mat(q_lw)}
 
 
+def make_track_frame_scene(seed: int, n_feat: int = 300, *, wrong_frac: float = 0.3, noise_px: float = 0.5,
+                           max_flips: int = 24, baseline_m: float = 0.15, rot_deg: float = 3.0, **track_kw):
+    """What Tracking::Track (tracking.cpp:267-279) reads: make_track_scene's last keyframe, landmarks and
+    current frame, plus a LAST FRAME that sees the same landmarks from T_lw = T_cl^-1 * T_cw (T_cl a
+    rotation of about rot_deg and a baseline of baseline_m), with make_last_frame_scene's descriptor
+    construction: last feature i's descriptor is the current keypoint train_of[i]'s with flips_last[i]
+    bits flipped, so Match(last, curr) returns `matches_last` (query i, train train_of[i]).  The current
+    pixels of the `wrong` features are random, so they are outliers of both paths (wrong_frac = 1.0:
+    both fail); whether PnP passes is the caller's to steer (flags, min_matches, min_inliers).
+
+    Returns make_track_scene's dict plus last_xy (n x 2 float32), desc_last, flips_last, matches_last,
+    pose_last (T_lw: qx qy qz qw tx ty tz, qw > 0), R_cl, t_cl."""
+    s = make_track_scene(seed, n_feat, wrong_frac=wrong_frac, noise_px=noise_px, max_flips=max_flips, **track_kw)
+    rng = np.random.default_rng([seed, 0x7F2A])
+    fx, fy, cx, cy = s["intr"]
+    q_cl = quat_from_rotvec(rng.normal(0, 1, 3) * np.deg2rad(rot_deg) / np.sqrt(3))
+    R_cl = quat_to_mat(q_cl)
+    d = rng.normal(0, 1, 3)
+    d[2] *= 0.3
+    t_cl = baseline_m * d / np.linalg.norm(d)
+    R_lw = R_cl.T @ s["R"]
+    t_lw = R_cl.T @ (s["t"] - t_cl)
+    pl = s["lm_pos"] @ R_lw.T + t_lw
+    last_xy = np.stack([fx * pl[:, 0] / pl[:, 2] + cx, fy * pl[:, 1] / pl[:, 2] + cy], -1) + rng.normal(0, noise_px, (n_feat, 2))
+    perm = s["train_of"]
+    flips = rng.integers(0, max_flips + 1, n_feat).astype(np.int32)
+    bits = np.unpackbits(s["desc_curr"][perm], axis=1)
+    for i in range(n_feat):
+        bits[i, rng.choice(256, flips[i], replace=False)] ^= 1
+    matches = np.zeros(n_feat, [("query_idx", "<i4"), ("train_idx", "<i4"), ("distance", "<f4")])
+    matches["query_idx"] = np.arange(n_feat)
+    matches["train_idx"] = perm
+    matches["distance"] = flips
+    # R -> quaternion through the rotation vector of R_lw's own quaternion product (qw > 0)
+    q_cw = s["pose"][:4]
+    q_lw = quat_mul(np.array([-q_cl[0], -q_cl[1], -q_cl[2], q_cl[3]]), q_cw)
+    if q_lw[3] < 0:
+        q_lw = -q_lw
+    return dict(s, last_xy=last_xy.astype(np.float32), desc_last=np.packbits(bits, axis=1), flips_last=flips,
+                matches_last=matches, pose_last=np.concatenate([q_lw, t_lw]), R_cl=R_cl, t_cl=t_cl)
+
+
 def make_sequence(seed: int, n_frames: int = 14, n_pts: int = 350, *, width: int = 640, height: int = 480,
                   intr=(FX, FY, CX, CY), step_m: float = 1.0, yaw_deg: float = 0.25, z_range=(5.0, 9.5),
                   depth_share: float = 0.5, noise_px: float = 0.3, max_flips: int = 10, garbage=(), dark=()):
