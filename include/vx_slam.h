@@ -1101,6 +1101,72 @@ int vx_dmap_create_keyframe_frame(vx_ctx* ctx, vx_dmap* map, uint64_t kf_id, con
                                   int cols, int64_t row_stride, uint64_t first_landmark_id,
                                   const vx_keyframe_options* opt, vx_keyframe_result* result);
 
+/* The frames 0 .. n_frames - 1 of batch bank `bank` (vx_orb_extract_batch_async) into n_frames handles
+ * in ONE launch of k_frame_capture_batch on ctx's stream (frame = grid y).  Each handle then holds
+ * what vx_frame_capture_async would have written from a slot with that frame's rows: count, overflow
+ * flag and rows, clamped to the handle's capacity.  Nothing synchronises.  VX_ERR_STATE when the
+ * bank holds fewer frames; VX_ERR_INVALID for a null / foreign-device / repeated handle. */
+int vx_frame_capture_batch_async(vx_ctx* ctx, int bank, int n_frames, vx_frame* const* frames);
+
+/* ---------------------------------------------------------------- Track() for a rig (track_rig.hip)
+ * <- Tracking::Track (tracking.cpp:267-279) for ALL cameras of a rig time step over one shared map as
+ *    ONE stream-ordered sequence and ONE synchronisation; every camera takes its own path (PnP,
+ *    fallback or neither), decided on the device:
+ *
+ *      Match(last_kf_i, curr_i) for all i  -> k_rig_pairs -> k_rig_pack -> k_pnp_* (P = cameras) -> k_rig_gate
+ *      Match(last_i, curr_i) under the gates -> k_rig_epairs -> k_rig_pack -> k_em_* (P = cameras)
+ *                                            -> k_rig_epose -> k_rig_final
+ *
+ *    The number of launches does not depend on the number of cameras.  Camera i's results are byte
+ *    for byte what vx_track_frame_async + vx_track_frame_fetch give for it alone. */
+#define VX_MAX_RIG_CAMERAS 16            /* = VX_MAX_MATCH_PAIRS */
+typedef struct {
+    uint64_t last_kf_id;                 /* keyframe of `map` whose features are last_kf's rows */
+    const vx_frame* last_kf;             /* NULL: this camera has no last keyframe (tracking.cpp:269) */
+    const vx_frame* last;                /* NULL: this camera's fallback fails (:282) */
+    const vx_frame* curr;
+    const double* pose_last7;            /* host; NULL = identity */
+    const double* intr4;                 /* host */
+} vx_rig_camera;
+
+/* One map, one ratio and one pair of option structs serve the whole rig; per camera the semantics,
+ * argument checks and ordering rules are vx_track_frame_async's (a camera needs `curr` and at least one
+ * of last_kf / last; last_kf == last is allowed: the fallback match is then run again under the gate,
+ * which gives list 0's rows and count when the gate is open).  n_cams in [1, VX_MAX_RIG_CAMERAS].
+ * Buffers: the call owns all of its buffers (match lists, pair and RANSAC scratch, packed result), so
+ * vx_track_frame_async, vx_track_pnp_async, vx_track_essential_async and the RANSAC entry points may
+ * run on ctx between the enqueue and the fetch, and a rig call between theirs.  May block at its start
+ * until the PREVIOUS vx_track_rig_async's argument table has left the pinned staging it reuses. */
+int vx_track_rig_async(vx_ctx* ctx, vx_dmap* map, int n_cams, const vx_rig_camera* cams, float ratio,
+                       const vx_track_options* pnp_opt, const vx_track_essential_options* ess_opt);
+/* One device-to-host copy of one packed block and one synchronisation for all cameras.  Camera i's part
+ * has vx_track_frame_fetch's layout (result | pair_match0 | mask0 | pair_match1 | mask1 | keypoint rows)
+ * at the offset vx_track_rig_layout returns for the call's capacities.  out: cap_cams records (NULL with
+ * cap_cams 0: counts only), *n_cams (may be NULL) the number of cameras; VX_ERR_CAPACITY when cap_cams is
+ * smaller.  with_keypoints = 0: the copy ends before the LAST camera's keypoint rows and
+ * vx_track_rig_keypoints is not available afterwards. */
+int vx_track_rig_fetch(vx_ctx* ctx, int with_keypoints, vx_track_frame_result* out, int cap_cams, int* n_cams);
+/* As vx_track_frame_pairs for camera `cam` of the fetched block.  No device work. */
+int vx_track_rig_pairs(vx_ctx* ctx, int cam, int which, int32_t* pair_match, uint8_t* mask, int cap_pairs);
+/* Camera cam's current-frame keypoint rows, a host copy out of the fetched block.  VX_ERR_CAPACITY
+ * (with *n set) when the count exceeds cap. */
+int vx_track_rig_keypoints(vx_ctx* ctx, int cam, vx_keypoint* kp, int cap, int* n);
+/* As vx_track_frame_matches for camera `cam`: the device list for vx_dmap_create_keyframe[_frame].
+ * Valid until the next vx_track_rig_async on ctx. */
+int vx_track_rig_matches(vx_ctx* ctx, int cam, int which, const vx_match** d_matches, const int32_t** d_n, int32_t* cap);
+/* The packed block's layout (pure host function, no context): camera i's part, sized by its pair
+ * capacities of the two paths and its keypoint capacity (each >= 0), starts at cam_offset[i] (16-byte
+ * aligned, ascending, parts disjoint); *total_bytes is the end of the last part.  Inside a part the
+ * offsets are vx_track_frame_fetch's.  VX_ERR_INVALID for n_cams outside [1, VX_MAX_RIG_CAMERAS], a
+ * null array or a negative capacity. */
+int vx_track_rig_layout(int n_cams, const int32_t* cap_pairs0, const int32_t* cap_pairs1, const int32_t* cap_kp,
+                        int64_t* cam_offset, int64_t* total_bytes);
+/* The fetched block itself (host memory, valid until the next fetch) and the capacities it was laid
+ * out with (each array cap_cams entries, any may be NULL): what a binding slices with
+ * vx_track_rig_layout.  VX_ERR_STATE before a fetch. */
+int vx_track_rig_block(vx_ctx* ctx, const uint8_t** block, int64_t* bytes, int32_t* cap_pairs0, int32_t* cap_pairs1,
+                       int32_t* cap_kp, int cap_cams);
+
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,
  * vx_match_device_async, vx_ba_plan_run_async), recorded once with every argument and replayed by

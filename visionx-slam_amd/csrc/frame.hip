@@ -63,6 +63,41 @@ __global__ void __launch_bounds__(kBlock) k_frame_capture(CaptureArgs a) {
     }
 }
 
+// The frames of a batch bank (vx_orb_extract_batch_async: frame-major rows, count of frame f at
+// src_count + 4 f) into one handle each in ONE launch: frame = blockIdx.y, and per frame exactly
+// k_frame_capture's copy, clamping and flags.  The handles' pointers travel as kernel arguments
+// (28 B a frame, 1.8 KB at VX_MAX_BATCH); a frame's row arrays start frame * src_cap rows into the bank,
+// so its keypoint range need not share the handle's 16-byte phase (grid_copy_range then moves dwords).
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): 16 VGPRs, 44 SGPRs, 0 B LDS, 0 B scratch.
+struct CaptureBatchArgs {
+    const uint8_t* src_kp;
+    const uint8_t* src_desc;
+    const int* src_count;
+    int src_cap;
+    uint8_t* dst_kp[VX_MAX_BATCH];
+    uint8_t* dst_desc[VX_MAX_BATCH];
+    int* dst_count[VX_MAX_BATCH];
+    int dst_cap[VX_MAX_BATCH];
+};
+
+__global__ void __launch_bounds__(kBlock) k_frame_capture_batch(CaptureBatchArgs a) {
+    const int f = blockIdx.y;
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x, nt = (size_t)gridDim.x * kBlock;
+    const int* src_count = a.src_count + 4 * (size_t)f;
+    const int dst_cap = a.dst_cap[f];
+    const int n_src = min(max(src_count[0], 0), a.src_cap);
+    const int n = min(n_src, dst_cap);
+    grid_copy_range(a.dst_kp[f], a.src_kp + (size_t)f * a.src_cap * sizeof(vx_keypoint), (size_t)n * sizeof(vx_keypoint), t, nt);
+    grid_copy_range(a.dst_desc[f], a.src_desc + (size_t)f * a.src_cap * 32, (size_t)n * 32, t, nt);
+    if (t == 0) {
+        int* dst_count = a.dst_count[f];
+        dst_count[0] = n;
+        dst_count[1] = (src_count[0] > dst_cap || src_count[1] != 0) ? 1 : 0;
+        dst_count[2] = 0;
+        dst_count[3] = 0;
+    }
+}
+
 int check_frame(vx_ctx* c, const vx_frame* f, const char* what) {
     if (!f || !f->block.p) return set_error(c, VX_ERR_INVALID, "%s: null frame", what);
     if (f->device != c->device) return set_error(c, VX_ERR_INVALID, "%s: frame and context on different devices", what);
@@ -129,6 +164,38 @@ int vx_frame_capture_async(vx_ctx* c, int slot, vx_frame* f) {
     const size_t items = (rows * sizeof(vx_keypoint) + 15) / 16 + 2 + rows * 2;  // uint4 items of the larger range + head / tail
     const int grid = (int)std::min<size_t>(kMaxWg, std::max<size_t>(1, (items + kBlock - 1) / kBlock));
     VX_HIP(c, launch(c, kStFrameCapture, k_frame_capture, dim3(grid), dim3(kBlock), 0, c->stream, a));
+    return VX_OK;
+}
+
+int vx_frame_capture_batch_async(vx_ctx* c, int bank, int n_frames, vx_frame* const* frames) {
+    if (!c) return VX_ERR_INVALID;
+    if (!frames) return set_error(c, VX_ERR_INVALID, "vx_frame_capture_batch_async: null frame list");
+    if (bank < 0 || bank >= VX_BATCH_BANKS) return set_error(c, VX_ERR_INVALID, "bad batch bank %d", bank);
+    if (n_frames < 1 || n_frames > c->batch_n[bank])
+        return set_error(c, VX_ERR_STATE, "batch bank %d holds %d frames, %d asked for", bank, c->batch_n[bank], n_frames);
+    const Slot& s = c->batch[bank];
+    CaptureBatchArgs a{};
+    a.src_kp = s.kp.as<uint8_t>();
+    a.src_desc = s.desc.as<uint8_t>();
+    a.src_count = s.count.as<int>();
+    a.src_cap = s.cap;
+    int max_cap = 1;
+    for (int i = 0; i < n_frames; ++i) {
+        int rc;
+        if ((rc = check_frame(c, frames[i], "vx_frame_capture_batch_async"))) return rc;
+        for (int j = 0; j < i; ++j)
+            if (frames[j] == frames[i]) return set_error(c, VX_ERR_INVALID, "vx_frame_capture_batch_async: frame %d given twice", i);
+        a.dst_kp[i] = reinterpret_cast<uint8_t*>(frames[i]->kp());
+        a.dst_desc[i] = frames[i]->desc();
+        a.dst_count[i] = frames[i]->count();
+        a.dst_cap[i] = frames[i]->cap;
+        max_cap = std::max(max_cap, frames[i]->cap);
+    }
+    VX_HIP(c, hipSetDevice(c->device));
+    const size_t rows = (size_t)std::min(s.cap, max_cap);
+    const size_t items = (rows * sizeof(vx_keypoint) + 15) / 16 + 2 + rows * 2;  // as vx_frame_capture_async, per frame
+    const int grid = (int)std::min<size_t>(kMaxWg, std::max<size_t>(1, (items + kBlock - 1) / kBlock));
+    VX_HIP(c, launch(c, kStFrameCaptureBatch, k_frame_capture_batch, dim3(grid, n_frames), dim3(kBlock), 0, c->stream, a));
     return VX_OK;
 }
 

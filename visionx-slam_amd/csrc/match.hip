@@ -416,8 +416,10 @@ int match_enqueue(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, con
     return rc;
 }
 
-int match_batch_enqueue(vx_ctx* c, const PairTab& tab, int n_pairs, int q_cap, int t_cap, float ratio) {
-    unsigned* best = c->mb_best.as<unsigned>();
+// the two launches of a batch into the caller's buffers: best holds n_pairs * q_cap keys, pair p's
+// matches go to out + p * q_cap and its count to out_count[4 p]
+int match_batch_launch(vx_ctx* c, const PairTab& tab, int n_pairs, int q_cap, int t_cap, float ratio, unsigned* best,
+                       vx_match* out, int* out_count) {
     // (two workgroups per CU over all the pairs: capped as in knn_rows_launch, the pairs' query
     // groups looped over)
     if (!c->n_cus) c->n_cus = std::max(vx_device_cus(c->device), 1);
@@ -426,12 +428,36 @@ int match_batch_enqueue(vx_ctx* c, const PairTab& tab, int n_pairs, int q_cap, i
                      c->stream, tab, q_cap, t_cap, ratio, best));
     ProfScope ps(c, kStMatchMerge);
     hipLaunchKernelGGL(k_knn_compact_batch, dim3(n_pairs), dim3(kMergeBlock), 0, c->stream, (const unsigned*)best, tab,
-                       q_cap, c->mb_matches.as<vx_match>(), c->mb_count.as<int>());
+                       q_cap, out, out_count);
     VX_LAUNCH_CHECK(c, "k_knn_compact_batch");
     return VX_OK;
 }
 
+// the context's own batch buffers: what vx_match_batch_async / vx_match_knn2_ratio_batch fill
+int match_batch_enqueue(vx_ctx* c, const PairTab& tab, int n_pairs, int q_cap, int t_cap, float ratio) {
+    return match_batch_launch(c, tab, n_pairs, q_cap, t_cap, ratio, c->mb_best.as<unsigned>(), c->mb_matches.as<vx_match>(),
+                              c->mb_count.as<int>());
+}
+
 }  // namespace
+
+// the launches of one batch into a caller's buffers (vx_internal.hpp)
+int match_batch_enqueue_to(vx_ctx* c, int n_pairs, const uint8_t* const* dq, const int* const* dnq,
+                           const uint8_t* const* dt, const int* const* dnt, int q_cap, int t_cap, float ratio,
+                           unsigned* best, vx_match* out, int* out_count) {
+    if (n_pairs < 1 || n_pairs > VX_MAX_MATCH_PAIRS || q_cap < 1 || t_cap < 0 || t_cap > (1 << 22))
+        return set_error(c, VX_ERR_INVALID, "match_batch_enqueue_to: %d pairs, capacities %d / %d", n_pairs, q_cap, t_cap);
+    PairTab tab;
+    std::memset(&tab, 0, sizeof tab);
+    for (int i = 0; i < n_pairs; ++i) {
+        tab.q[i] = dq[i];
+        tab.nq[i] = dnq[i];
+        tab.t[i] = dt[i];
+        tab.nt[i] = dnt[i];
+    }
+    return match_batch_launch(c, tab, n_pairs, q_cap, t_cap, ratio, best, out, out_count);
+}
+
 }  // namespace vx
 
 using namespace vx;

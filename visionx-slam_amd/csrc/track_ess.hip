@@ -35,188 +35,26 @@
 #include <cstring>
 
 #include "vx_internal.hpp"
-#include "track_common.hpp"
+#include "track_bodies.hpp"
 
 namespace vx {
 namespace {
 
-using trk::block_rank;
 using trk::kBlock;
 using trk::kWaves;
 
-struct EPairArgs {
-    // match list (query = last frame feature, train = current frame feature)
-    const vx_match* matches;
-    const int* n_matches;
-    int cap_matches;
-    // positions: two floats at *_xy + i * stride, *n_* rows
-    const uint8_t* last_xy;
-    int64_t last_stride;
-    const int* n_last;
-    const uint8_t* curr_xy;
-    int64_t curr_stride;
-    const int* n_curr;
-    // options
-    int min_matches;
-    vx_essential_options ess;
-    double intr[4];
-    // scratch + outputs
-    int* good;              // cap_matches: kept match indices, match order
-    float* p1;              // 2 per pair (pts_last)
-    float* p2;              // 2 per pair (pts_curr)
-    int* pair_match;        // per pair
-    uint8_t* mask;          // per pair (zeroed here, written by k_em_cheir / k_em_final)
-    vx_track_essential_result* res;
-    int* offsets;           // 2
-    double* intr_out;       // 4
-    vx_essential_options* opt_out;
-};
+using trk::EPairArgs;
+using trk::EPoseArgs;
 
+// the stages above, stated in track_epairs_body.inc (shared with k_rig_epairs, track_rig.hip)
 __global__ void __launch_bounds__(kBlock) k_track_epairs(EPairArgs a) {
-    __shared__ int s_cnt[kWaves];
-    __shared__ float s_min[kWaves];
-    __shared__ double s_sum[kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = min(max(*a.n_matches, 0), a.cap_matches);
-    const int n_last = *a.n_last, n_curr = *a.n_curr;
-
-    // 1-3: min distance, threshold, the kept matches in match order (track_common.hpp)
-    float mn;
-    const int n_good = trk::filter_matches(a.matches, n, a.good, s_cnt, s_min, &mn);
-
-    // 4 + 5: pairs in kept-match order, parallax partials
-    const bool enough = n_good >= a.min_matches;
-    int n_pairs = 0, n_bad = 0;
-    double part = 0.0;
-    for (int base = 0; base < n_good; base += kBlock) {
-        const int j = base + tid;
-        bool pair = false, bad_index = false;
-        int mi = 0;
-        float lx = 0.f, ly = 0.f, cx = 0.f, cy = 0.f;
-        if (j < n_good) {
-            mi = a.good[j];
-            const vx_match m = a.matches[mi];
-            if (m.query_idx < 0 || m.query_idx >= n_last || m.train_idx < 0 || m.train_idx >= n_curr) {
-                bad_index = true;
-            } else {
-                const float* pl = reinterpret_cast<const float*>(a.last_xy + (int64_t)m.query_idx * a.last_stride);
-                const float* pc = reinterpret_cast<const float*>(a.curr_xy + (int64_t)m.train_idx * a.curr_stride);
-                lx = pl[0];
-                ly = pl[1];
-                cx = pc[0];
-                cy = pc[1];
-                pair = true;
-                if (enough) {  // ComputeParallax (:548-560): (p1 - p2).norm() in double
-                    const double dx = (double)lx - (double)cx;
-                    const double dy = (double)ly - (double)cy;
-                    part += sqrt(dx * dx + dy * dy);
-                }
-            }
-        }
-        int total;
-        const int r = block_rank(pair, s_cnt, &total);
-        if (pair) {
-            const int k = n_pairs + r;
-            a.p1[2 * k] = lx;
-            a.p1[2 * k + 1] = ly;
-            a.p2[2 * k] = cx;
-            a.p2[2 * k + 1] = cy;
-            a.pair_match[k] = mi;
-            a.mask[k] = 0;
-        }
-        n_pairs += total;
-        n_bad += bad_index ? 1 : 0;
-    }
-
-    // 5: parallax (and the skipped-index count), fixed order
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        part += __shfl_xor(part, off);
-        n_bad += __shfl_xor(n_bad, off);
-    }
-    if (lane == 0) {
-        s_sum[wave] = part;
-        s_cnt[wave] = n_bad;
-    }
-    __syncthreads();
-
-    // 6: result counts and the essential problem record
-    if (tid == 0) {
-        double sum = s_sum[0];
-        n_bad = s_cnt[0];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) {
-            sum += s_sum[w];
-            n_bad += s_cnt[w];
-        }
-        vx_track_essential_result* r = a.res;
-        r->status = 0;
-        r->n_matches = n;
-        r->n_good_matches = n_good;
-        r->n_pairs = n_pairs;
-        r->n_bad_index = n_bad;
-        r->min_distance = mn;
-        r->parallax = enough && n_good > 0 ? sum / (double)n_good : 0.0;  // cnt > 0 ? sum / cnt : 0 (:559)
-        a.offsets[0] = 0;
-        a.offsets[1] = enough ? n_pairs : 0;  // (:306)
-        for (int k = 0; k < 4; ++k) a.intr_out[k] = a.intr[k];
-        *a.opt_out = a.ess;
-    }
+#include "track_epairs_body.inc"
 }
-
-struct EPoseArgs {
-    vx_track_essential_result* res;
-    double pose_last[7];  // T_lw: qx qy qz qw tx ty tz
-};
 
 // Sophus::SE3d(R, t) * T_lw by one lane (tracking.cpp:539-541); zero when recoverPose gave nothing
 __global__ void __launch_bounds__(64) k_track_epose(EPoseArgs a) {
     if (threadIdx.x != 0) return;
-    const vx_essential_result* e = &a.res->ess;
-    double out[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (e->ok) {
-        double R[9];
-        for (int k = 0; k < 9; ++k) R[k] = e->R[k];
-        // q_cl: Shepperd's method, as PoseFromRt (Eigen::Quaterniond(Matrix3d))
-        double x, y, z, w;
-        const double tr = R[0] + R[4] + R[8];
-        if (tr > 0.0) {
-            const double s = sqrt(tr + 1.0) * 2.0;
-            w = 0.25 * s; x = (R[7] - R[5]) / s; y = (R[2] - R[6]) / s; z = (R[3] - R[1]) / s;
-        } else if (R[0] > R[4] && R[0] > R[8]) {
-            const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
-            w = (R[7] - R[5]) / s; x = 0.25 * s; y = (R[1] + R[3]) / s; z = (R[2] + R[6]) / s;
-        } else if (R[4] > R[8]) {
-            const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
-            w = (R[2] - R[6]) / s; x = (R[1] + R[3]) / s; y = 0.25 * s; z = (R[5] + R[7]) / s;
-        } else {
-            const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
-            w = (R[3] - R[1]) / s; x = (R[2] + R[6]) / s; y = (R[5] + R[7]) / s; z = 0.25 * s;
-        }
-        const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
-        const double ax = x * inv, ay = y * inv, az = z * inv, aw = w * inv;
-        const double bx = a.pose_last[0], by = a.pose_last[1], bz = a.pose_last[2], bw = a.pose_last[3];
-        // q = q_cl (x) q_lw, Eigen's coefficient order
-        double qw = aw * bw - ax * bx - ay * by - az * bz;
-        double qx = aw * bx + ax * bw + ay * bz - az * by;
-        double qy = aw * by + ay * bw + az * bx - ax * bz;
-        double qz = aw * bz + az * bw + ax * by - ay * bx;
-        // Sophus's first-order renormalisation
-        const double n2 = qx * qx + qy * qy + qz * qz + qw * qw;
-        if (n2 != 1.0) {
-            const double sc = 2.0 / (1.0 + n2);
-            qx *= sc; qy *= sc; qz *= sc; qw *= sc;
-        }
-        // t = T_cl * t_lw (SE3d::operator*(Vec3d))
-        const double px = a.pose_last[4], py = a.pose_last[5], pz = a.pose_last[6];
-        const double ux = ay * pz - az * py, uy = az * px - ax * pz, uz = ax * py - ay * px;
-        const double wx = 2 * ux, wy = 2 * uy, wz = 2 * uz;
-        out[0] = qx; out[1] = qy; out[2] = qz; out[3] = qw;
-        out[4] = px + aw * wx + (ay * wz - az * wy) + e->t[0];
-        out[5] = py + aw * wy + (az * wx - ax * wz) + e->t[1];
-        out[6] = pz + aw * wz + (ax * wy - ay * wx) + e->t[2];
-    }
-    for (int k = 0; k < 7; ++k) a.res->pose[k] = out[k];
+    trk::track_epose(a);
 }
 
 // packed result block: vx_track_essential_result | pair_match[cap] | mask[cap] (track_common.hpp)

@@ -36,8 +36,7 @@
 
 #include "vx_internal.hpp"
 #include "dmap.hpp"
-#include "track_common.hpp"
-#include "vx_rows.hpp"
+#include "track_bodies.hpp"
 
 namespace vx {
 namespace {
@@ -48,101 +47,20 @@ constexpr int kFinalMaxWg = 64;
 
 using trk::align16;
 
-struct GateArgs {
-    const vx_track_result* pnp;  // NULL: no last keyframe
-    int min_matches, min_inliers;
-    const int* n_last;           // NULL: no last frame
-    int cap_last;
-    const int* n_matches0;       // list 0's count, when list 1 shares its rows (else NULL)
-    int* n_matches1;             // ... and list 1's gated count
-    int* gate;                   // {gated query count, PnP status, gate open, 0}
-};
+using trk::FinalArgs;
+using trk::GateArgs;
 
-// One workgroup; one lane has all the work (a record read, a rule, four stores)
+// One workgroup; one lane has all the work (a record read, a rule, four stores: track_bodies.hpp)
 __global__ void __launch_bounds__(kGateBlock) k_track_gate(GateArgs a) {
     if (threadIdx.x != 0) return;
-    const int status = a.pnp ? trk::pnp_status(*a.pnp, a.min_matches, a.min_inliers) : VX_TRACK_OK;
-    const bool open = !a.pnp || status != VX_TRACK_OK;  // (:269-273)
-    a.gate[0] = open && a.n_last ? min(max(*a.n_last, 0), a.cap_last) : 0;
-    a.gate[1] = status;
-    a.gate[2] = open ? 1 : 0;
-    a.gate[3] = 0;
-    if (a.n_matches0) *a.n_matches1 = open ? *a.n_matches0 : 0;
+    trk::track_gate(a);
 }
 
-struct FinalArgs {
-    const uint8_t* tk;   // vx_track_pnp_async's packed block (NULL: no last keyframe)
-    int tk_cap;
-    const uint8_t* te;   // vx_track_essential_async's packed block
-    int te_cap;
-    const int* gate;
-    int has_last;
-    int ess_min_matches, ess_min_inliers;
-    const uint8_t* kp;   // the current frame's keypoint rows
-    const int* n_kp;
-    int cap_kp;
-    uint8_t* out;
-    size_t o_pm0, o_mask0, o_pm1, o_mask1, o_kp;
-};
-
+// (the body: track_bodies.hpp, shared with k_rig_final; the masks are the two packed blocks' own)
 __global__ void __launch_bounds__(kFinalBlock) k_track_final(FinalArgs a) {
     const size_t t = (size_t)blockIdx.x * kFinalBlock + threadIdx.x, nt = (size_t)gridDim.x * kFinalBlock;
-    vx_track_frame_result* out = reinterpret_cast<vx_track_frame_result*>(a.out);
-    const vx_track_essential_result* er = reinterpret_cast<const vx_track_essential_result*>(a.te);
-    // the records without their first dword (status: written below by the lane that evaluates it)
-    uint32_t* o_pnp = reinterpret_cast<uint32_t*>(&out->pnp);
-    if (a.tk) {
-        const vx_track_result* pr = reinterpret_cast<const vx_track_result*>(a.tk);
-        grid_copy_range(o_pnp + 1, reinterpret_cast<const uint32_t*>(pr) + 1, sizeof(vx_track_result) - 4, t, nt);
-        const int np = min(max(pr->n_pairs, 0), a.tk_cap);
-        grid_copy_range(a.out + a.o_pm0, a.tk + trk::off_pair_match<vx_track_result>(), (size_t)np * 4, t, nt);
-        grid_copy_range(a.out + a.o_mask0, a.tk + trk::off_mask<vx_track_result>(a.tk_cap), ((size_t)np + 3) & ~(size_t)3, t, nt);
-    } else {
-        for (size_t k = 1 + t; k < sizeof(vx_track_result) / 4; k += nt) o_pnp[k] = 0;
-    }
-    grid_copy_range(reinterpret_cast<uint32_t*>(&out->ess) + 1, reinterpret_cast<const uint32_t*>(er) + 1,
-                    sizeof(vx_track_essential_result) - 4, t, nt);
-    const int ne = min(max(er->n_pairs, 0), a.te_cap);
-    grid_copy_range(a.out + a.o_pm1, a.te + trk::off_pair_match<vx_track_essential_result>(), (size_t)ne * 4, t, nt);
-    grid_copy_range(a.out + a.o_mask1, a.te + trk::off_mask<vx_track_essential_result>(a.te_cap), ((size_t)ne + 3) & ~(size_t)3, t, nt);
-    const int nk = min(max(*a.n_kp, 0), a.cap_kp);
-    grid_copy_range(a.out + a.o_kp, a.kp, (size_t)nk * sizeof(vx_keypoint), t, nt);
-    if (t != 0) return;
-
-    const int pnp_ran = a.tk ? 1 : 0, open = a.gate[2];
-    const int ess_ran = open && a.has_last ? 1 : 0;
-    const int pnp_st = a.gate[1];
-    const int ess_st = trk::ess_status(*er, a.ess_min_matches, a.ess_min_inliers);  // (:306, :317)
-    out->pnp.status = pnp_ran ? pnp_st : 0;
-    out->ess.status = ess_st;
-    int path = VX_TRACK_PATH_NONE, status, n_inliers = 0;
-    double parallax = 0.0, pose[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (pnp_ran && pnp_st == VX_TRACK_OK) {  // (:269-273)
-        const vx_track_result* pr = reinterpret_cast<const vx_track_result*>(a.tk);
-        path = VX_TRACK_PATH_PNP;
-        status = VX_TRACK_OK;
-        n_inliers = pr->pnp.n_inliers;
-        parallax = pr->parallax;
-        for (int k = 0; k < 7; ++k) pose[k] = pr->pnp.pose[k];
-    } else if (ess_ran) {  // (:278)
-        status = ess_st;
-        if (ess_st == VX_TRACK_OK) {
-            path = VX_TRACK_PATH_ESSENTIAL;
-            n_inliers = er->ess.n_inliers;
-            parallax = er->parallax;
-            for (int k = 0; k < 7; ++k) pose[k] = er->pose[k];
-        }
-    } else {
-        status = pnp_st;  // no last frame (:282): PnP's failure stands
-    }
-    out->path = path;
-    out->status = status;
-    out->n_inliers = n_inliers;
-    out->n_keypoints = nk;
-    out->parallax = parallax;
-    for (int k = 0; k < 7; ++k) out->pose[k] = pose[k];
-    out->pnp_ran = pnp_ran;
-    out->ess_ran = ess_ran;
+    trk::track_final<false>(a, a.tk + trk::off_mask<vx_track_result>(a.tk_cap),
+                            a.te + trk::off_mask<vx_track_essential_result>(a.te_cap), t, nt);
 }
 
 }  // namespace

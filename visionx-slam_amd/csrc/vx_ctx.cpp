@@ -174,7 +174,9 @@ static const char* kStageNames[vx::kStCount] = {
     "em_hypotheses",  "em_select",     "ba_iter",         "ba_prologue",
     "ba_window",      "track_pairs",   "kf_features",     "kf_matches",  "kf_commit",
     "track_epairs",   "track_epose",   "init_sums",       "init_gate",
-    "frame_capture",  "track_gate",    "track_final"};
+    "frame_capture",  "track_gate",    "track_final",
+    "rig_pairs",      "rig_pack",      "rig_gate",        "rig_epairs",  "rig_epose",
+    "rig_final",      "frame_capture_batch"};
 
 extern "C" {
 
@@ -248,7 +250,7 @@ void vx_destroy(vx_ctx* c) {
     if (c->snap_map) vx_dmap_destroy(c->snap_map);
     vx::plan_pool_release(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto e : {c->order_event, c->tk_in_event, c->te_in_event, c->ig_in_event, c->fr_in_event})
+    for (auto e : {c->order_event, c->tk_in_event, c->te_in_event, c->ig_in_event, c->fr_in_event, c->tr_tab_event})
         if (e) (void)hipEventDestroy(e);
 #ifndef VX_NO_RCCL
     if (c->comm) ncclCommDestroy(c->comm);

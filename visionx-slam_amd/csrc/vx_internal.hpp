@@ -77,6 +77,13 @@ enum Stage : int {
     kStFrameCapture,  // a slot's rows into a device-resident frame (k_frame_capture)
     kStTrackGate,     // Track()'s PnP -> essential fallback decision (k_track_gate)
     kStTrackFinal,    // its result head and packed block (k_track_final)
+    kStRigPairs,      // Track() for a rig: k_track_pairs' stages, camera = workgroup (k_rig_pairs)
+    kStRigPack,       // the cameras' pair segments into the contiguous RANSAC arrays (k_rig_pack)
+    kStRigGate,       // the fallback decision per camera (k_rig_gate)
+    kStRigEPairs,     // k_track_epairs' stages, camera = workgroup (k_rig_epairs)
+    kStRigEPose,      // T_cl * T_lw per camera (k_rig_epose)
+    kStRigFinal,      // the cameras' heads and packed blocks (k_rig_final)
+    kStFrameCaptureBatch,  // a batch bank's frames into resident frames (k_frame_capture_batch)
     kStCount
 };
 
@@ -288,6 +295,30 @@ struct vx_ctx {
     bool tf_list1_own = true;    // false: list 1 is list 0's rows under a gated count (last_kf == last)
     bool tf_valid = false, tf_fetched = false;
 
+    // ---- Track() for a rig (track_rig.hip): buffers of its own throughout, so a single-camera track
+    // (tk_*, te_*, tf_*) may be in flight on the same context
+    vx::PinnedBuf tr_tab_host;   // the per-camera argument table, staged for one upload ...
+    vx::DevBuf tr_tab;           // ... into one device block
+    hipEvent_t tr_tab_event = nullptr;  // (recorded after that upload: the staging is reused once it has passed)
+    vx::DevBuf tr_match;         // match scratch, both lists of every camera, their counts, the gate records
+    vx::DevBuf tr_zero;          // int32[4] of zeros: the query count of a camera without a last keyframe (never written)
+    vx::DevBuf tr_work;          // kept-match lists, pair segments, contiguous RANSAC arrays + masks, problem
+                                 // records, RANSAC results, the cameras' packed PnP / essential blocks
+    vx::DevBuf tr_hyp[2];        // hypothesis scratch of the two RANSACs
+    vx::DevBuf tr_out;           // the packed result, camera blocks at vx_track_rig_layout's offsets
+    vx::PinnedBuf tr_host;
+    struct RigCam {
+        int cap[2] = {0, 0};       // match capacities (0: list 0 not enqueued: no last keyframe)
+        int pair_cap[2] = {0, 0};  // pair capacities of the two paths
+        int cap_kp = 0;
+        const vx_match* list[2] = {nullptr, nullptr};
+        const int32_t* count[2] = {nullptr, nullptr};
+        int64_t offset = 0;        // of the camera's block in tr_out / tr_host
+    } tr_cam[VX_MAX_RIG_CAMERAS];
+    int tr_n = 0;                // cameras of the enqueued call
+    int64_t tr_bytes = 0;        // of the packed result
+    bool tr_valid = false, tr_fetched = false, tr_fetched_kp = false;
+
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {
         vx::DevBuf wptr, wlm, wfl, cam, wid, wuv, lid, bad, optr, okf, ofi, pos, hkey, hval, f_lm, f_pv, f_first,
@@ -370,6 +401,14 @@ int orb_prepare(vx_ctx* c, const vx_orb_params* p, int w, int h);
 // on c->stream, nothing synchronised.  vx_match_* pass the context's own list (c->matches).
 int match_enqueue_to(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, const uint8_t* dt, const int* dnt,
                      int nt_host, int q_cap, int t_cap, float ratio, vx_match* out, int* out_count);
+// The batched form (k_knn_rows_batch + k_knn_compact_batch: pair = grid y / workgroup) into a caller's
+// buffers: n_pairs in [1, VX_MAX_MATCH_PAIRS] pairs under ONE q_cap / t_cap (every pair's device
+// counts are clamped to them); `best` holds n_pairs * q_cap keys of scratch, pair p's matches go to
+// out + p * q_cap and its count to out_count[4 p].  No context buffer is used.  Per pair the list is
+// match_enqueue_to's, byte for byte.  vx_match_batch_async passes the context's own buffers (c->mb_*).
+int match_batch_enqueue_to(vx_ctx* c, int n_pairs, const uint8_t* const* dq, const int* const* dnq,
+                           const uint8_t* const* dt, const int* const* dnt, int q_cap, int t_cap, float ratio,
+                           unsigned* best, vx_match* out, int* out_count);
 
 // PnP RANSAC on problems already in device memory (ransac.hip): k_pnp_hyp over (hmax, P) and
 // k_pnp_refine over P enqueued on c->stream, nothing synchronised.  Problem p owns correspondences

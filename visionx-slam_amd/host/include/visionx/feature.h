@@ -50,6 +50,12 @@ public:
     // Descriptors() are left untouched (FrameTracker::TrackResident fills Features(), Materialize both).
     void UseContext(vx_ctx* ctx) { ctx_ = ctx; }
     void ExtractResident(Frame& frame);
+    // The rig form: the images of every frame of one time step uploaded, extracted in one batched launch
+    // sequence (vx_orb_extract_batch) and captured into the frames' device handles in ONE launch
+    // (vx_frame_capture_batch_async).  Each handle then holds what ExtractResident(frame) leaves there; no
+    // synchronisation.  Frames of differing size or channel count, empty ones, or more than VX_MAX_BATCH
+    // are extracted one by one.
+    void ExtractResidentBatch(const std::vector<Frame::Ptr>& frames);
 
 private:
     vx_ctx* ctx_ = nullptr;

@@ -131,7 +131,24 @@ public:
     // with no last keyframe and T_lw = identity, then the parallax gate; sets Essential()'s LastInliers /
     // LastParallax as EstimateInitialPose does and fills current->Features().
     bool EstimateInitialPoseResident(const Frame::Ptr& init, const Frame::Ptr& current);
-    // The device match list the last resident call holds for Match(query, train), by frame ids
+    // Track() for every camera of a rig time step over the one resident map: ONE vx_track_rig_async and one
+    // fetch (csrc/track_rig.hip), each camera taking its own path on the device.  Per camera it returns
+    // what TrackResident returns, sets the pose and fills current->Features() as TrackResident does, and
+    // keeps UsedFallback / LastInliers / LastParallax per camera index (RigUsedFallback, ...; the last two
+    // kept on failure, as the single trackers keep theirs).  At most VX_MAX_RIG_CAMERAS cameras
+    // (std::invalid_argument beyond); a camera TrackResident would refuse without a device call (no
+    // current frame, no camera model, neither a last keyframe nor a last frame) returns false and stays
+    // out of the call.  The component trackers' own LastInliers / UsedFallback are not touched.
+    struct RigCamera {
+        Frame::Ptr last_keyframe, last_frame, current;
+    };
+    std::vector<bool> TrackRig(const std::vector<RigCamera>& cams);
+    bool RigUsedFallback(size_t cam) const { return rig_.at(cam).used_fallback; }
+    int RigLastInliers(size_t cam) const { const RigState& r = rig_.at(cam); return r.used_fallback ? r.ess_inliers : r.pnp_inliers; }
+    double RigLastParallax(size_t cam) const { const RigState& r = rig_.at(cam); return r.used_fallback ? r.ess_parallax : r.pnp_parallax; }
+    const vx_track_frame_result& RigResult(size_t cam) const { return rig_.at(cam).result; }
+    // The device match list the last resident call (TrackResident, EstimateInitialPoseResident or TrackRig:
+    // each keeps its own) holds for Match(query, train), by frame ids
     // (tracking.cpp:340 and :863, and :208 and :863, match the same two frames): false when it holds none.
     bool MatchList(uint64_t query_id, uint64_t train_id, const vx_match** d_matches, const int32_t** d_n, int32_t* cap) const;
     // Resident calls use ONE ratio for both matches (the matcher's nn_ratio, set by Tracking::UseResidentFrames);
@@ -158,6 +175,17 @@ private:
     // (query frame id, train frame id) of the two device match lists of the last resident call
     uint64_t list_ids_[2][2] = {{0, 0}, {0, 0}};
     bool list_valid_[2] = {false, false};
+    // per rig camera: its state across calls and the ids of its two device lists of the last TrackRig
+    struct RigState {
+        bool used_fallback = false;
+        int pnp_inliers = 0, ess_inliers = 0;
+        double pnp_parallax = 0.0, ess_parallax = 0.0;
+        vx_track_frame_result result{};
+        int slot = -1;  // the camera's index in the last vx_track_rig_async (-1: it stayed out)
+        uint64_t list_ids[2][2] = {{0, 0}, {0, 0}};
+        bool list_valid[2] = {false, false};
+    };
+    std::vector<RigState> rig_;
 };
 
 }  // namespace visionx

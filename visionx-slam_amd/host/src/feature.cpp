@@ -125,6 +125,30 @@ void ORBExtractor::ExtractResident(Frame& frame) {
           "vx_frame_extract_host_async");
 }
 
+void ORBExtractor::ExtractResidentBatch(const std::vector<Frame::Ptr>& frames) {
+    if (frames.empty()) return;
+    const ImageU8& i0 = frames[0]->Image();
+    bool uniform = (int)frames.size() <= VX_MAX_BATCH && !i0.empty();
+    for (const auto& f : frames)
+        uniform = uniform && f->Image().rows == i0.rows && f->Image().cols == i0.cols &&
+                  f->Image().channels == i0.channels && f->Image().step() == i0.step() && !f->Image().empty();
+    if (!uniform) {
+        for (const auto& f : frames) ExtractResident(*f);
+        return;
+    }
+    vx_ctx* c = ctx_ ? ctx_ : vxhost::ThreadContext();
+    std::vector<const uint8_t*> imgs;
+    std::vector<vx_frame*> handles;
+    for (const auto& f : frames) {
+        imgs.push_back(f->Image().ptr());
+        handles.push_back(ResidentHandle(c, *f, 2 * params_.n_features + 256));
+    }
+    check(c, vx_orb_extract_batch(c, &params_, imgs.data(), (int)frames.size(), i0.cols, i0.rows, i0.channels,
+                                  (int64_t)i0.step(), 0),
+          "vx_orb_extract_batch");
+    check(c, vx_frame_capture_batch_async(c, 0, (int)frames.size(), handles.data()), "vx_frame_capture_batch_async");
+}
+
 void UploadResident(vx_ctx* c, Frame& frame, const float* xy, const uint8_t* desc, int n) {
     check(c, vx_frame_upload_async(c, ResidentHandle(c, frame, std::max(n, 1)), xy, desc, n), "vx_frame_upload_async");
 }

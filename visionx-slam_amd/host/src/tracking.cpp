@@ -1,6 +1,7 @@
 // tracking.cpp — visionx::PnPTracker over vx_track_pnp_host_async / vx_track_pnp_fetch (see tracking.h).
 #include "visionx/tracking.h"
 
+#include <array>
 #include <cmath>
 #include <stdexcept>
 #include <string>
@@ -153,6 +154,10 @@ bool FrameTracker::MatchList(uint64_t query_id, uint64_t train_id, const vx_matc
     for (int which = 0; which < 2; ++which)
         if (list_valid_[which] && list_ids_[which][0] == query_id && list_ids_[which][1] == train_id)
             return vx_track_frame_matches(pnp_.map_->context(), which, d_matches, d_n, cap) == VX_OK;
+    for (const RigState& r : rig_)
+        for (int which = 0; which < 2; ++which)
+            if (r.slot >= 0 && r.list_valid[which] && r.list_ids[which][0] == query_id && r.list_ids[which][1] == train_id)
+                return vx_track_rig_matches(pnp_.map_->context(), r.slot, which, d_matches, d_n, cap) == VX_OK;
     return false;
 }
 
@@ -231,6 +236,106 @@ bool FrameTracker::TrackResident(const Frame::Ptr& last_keyframe, const Frame::P
     essential_.last_inliers_ = resident_.n_inliers;
     essential_.last_parallax_ = resident_.parallax;
     return true;
+}
+
+std::vector<bool> FrameTracker::TrackRig(const std::vector<RigCamera>& cams) {
+    if (cams.size() > (size_t)VX_MAX_RIG_CAMERAS) throw std::invalid_argument("FrameTracker::TrackRig: more than VX_MAX_RIG_CAMERAS cameras");
+    if (pnp_.options_.nn_ratio != essential_.options_.nn_ratio)
+        throw std::invalid_argument("FrameTracker: resident calls take one nn_ratio for both matches (SetRatio)");
+    std::vector<bool> ok(cams.size(), false);
+    rig_.resize(std::max(rig_.size(), cams.size()));
+    for (RigState& r : rig_) {
+        r.slot = -1;
+        r.list_valid[0] = r.list_valid[1] = false;
+    }
+    // the cameras of the device call, with the host arrays their table entries point to
+    std::vector<vx_rig_camera> table;
+    std::vector<size_t> index;
+    std::vector<std::array<double, 11>> host(cams.size());  // intr4 | pose_last7
+    for (size_t i = 0; i < cams.size(); ++i) {
+        const RigCamera& k = cams[i];
+        rig_[i].used_fallback = false;
+        if (!k.current) continue;  // tracking.cpp:333-336, :282-285
+        if (!k.current->GetCamera() || (!k.last_keyframe && !k.last_frame)) {
+            rig_[i].used_fallback = true;  // Track() gets to TrackLastFrame, which returns false (:282-285, :516)
+            continue;
+        }
+        for (const Frame::Ptr& f : {k.last_keyframe, k.last_frame, k.current})
+            if (f && !f->Resident()) throw std::invalid_argument("FrameTracker: a frame without a resident handle");
+        const auto cam = k.current->GetCamera();
+        host[i] = {cam->fx(), cam->fy(), cam->cx(), cam->cy(), 0, 0, 0, 1, 0, 0, 0};
+        if (k.last_frame) {
+            const SE3d L = k.last_frame->Pose();
+            const double p[7] = {L.qx, L.qy, L.qz, L.qw, L.tx, L.ty, L.tz};
+            for (int j = 0; j < 7; ++j) host[i][4 + j] = p[j];
+        }
+        vx_rig_camera t{};
+        t.last_kf_id = k.last_keyframe ? k.last_keyframe->Id() : 0;
+        t.last_kf = k.last_keyframe ? k.last_keyframe->Resident()->handle() : nullptr;
+        t.last = k.last_frame ? k.last_frame->Resident()->handle() : nullptr;
+        t.curr = k.current->Resident()->handle();
+        t.intr4 = host[i].data();
+        t.pose_last7 = host[i].data() + 4;
+        rig_[i].slot = (int)table.size();
+        table.push_back(t);
+        index.push_back(i);
+    }
+    if (table.empty()) return ok;
+    DeviceMap::Ptr& map = pnp_.map_;
+    map->Flush();
+    vx_track_options po;
+    vx_track_default_options(&po);
+    po.min_matches = pnp_.options_.min_matches;
+    po.min_inliers = pnp_.options_.min_inliers;
+    po.pnp.reproj_error = pnp_.options_.max_reproj_error;
+    vx_track_essential_options eo;
+    vx_track_essential_default_options(&eo);
+    eo.min_matches = essential_.options_.min_matches;
+    eo.min_inliers = essential_.options_.min_inliers;
+    vx_ctx* c = map->context();
+    int rc = vx_track_rig_async(c, map->handle(), (int)table.size(), table.data(), pnp_.options_.nn_ratio, &po, &eo);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_rig_async: ") + vx_last_error(c));
+    std::vector<vx_track_frame_result> res(table.size());
+    rc = vx_track_rig_fetch(c, 1, res.data(), (int)res.size(), nullptr);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_rig_fetch: ") + vx_last_error(c));
+    for (size_t s = 0; s < table.size(); ++s) {
+        const size_t i = index[s];
+        const RigCamera& k = cams[i];
+        RigState& r = rig_[i];
+        r.result = res[s];
+        kp_.resize((size_t)k.current->Resident()->capacity());
+        int n = 0;
+        rc = vx_track_rig_keypoints(c, (int)s, kp_.data(), (int)kp_.size(), &n);
+        if (rc != VX_OK) throw std::runtime_error(std::string("vx_track_rig_keypoints: ") + vx_last_error(c));
+        auto& feats = k.current->Features();  // as RunResident fills them
+        feats.assign((size_t)n, Feature());
+        for (int j = 0; j < n; ++j) {
+            feats[j].position = Vec2d(kp_[j].x, kp_[j].y);
+            feats[j].response = kp_[j].response;
+        }
+        if (k.last_keyframe) {
+            r.list_ids[0][0] = k.last_keyframe->Id(), r.list_ids[0][1] = k.current->Id();
+            r.list_valid[0] = true;
+        }
+        if (k.last_frame && r.result.ess_ran) {  // (a closed gate leaves list 1 empty)
+            r.list_ids[1][0] = k.last_frame->Id(), r.list_ids[1][1] = k.current->Id();
+            r.list_valid[1] = true;
+        }
+        if (r.result.path == VX_TRACK_PATH_PNP) {  // as TrackResident (:443-450)
+            SetPose7(k.current, r.result.pose);
+            r.pnp_parallax = r.result.parallax;
+            r.pnp_inliers = r.result.n_inliers;
+            ok[i] = true;
+            continue;
+        }
+        r.used_fallback = true;
+        if (r.result.path != VX_TRACK_PATH_ESSENTIAL) continue;
+        SetPose7(k.current, r.result.pose);  // (:539-541, :324-325)
+        r.ess_inliers = r.result.n_inliers;
+        r.ess_parallax = r.result.parallax;
+        ok[i] = true;
+    }
+    return ok;
 }
 
 bool FrameTracker::EstimateInitialPoseResident(const Frame::Ptr& init, const Frame::Ptr& current) {

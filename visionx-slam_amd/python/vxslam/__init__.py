@@ -108,6 +108,8 @@ EXPORTS = [
     "vx_frame_upload_async", "vx_frame_device", "vx_frame_fetch", "vx_frame_fetch_ex",
     "vx_track_frame_async", "vx_track_frame_fetch", "vx_track_frame_pairs", "vx_track_frame_matches",
     "vx_dmap_create_keyframe_frame",
+    "vx_frame_capture_batch_async", "vx_track_rig_async", "vx_track_rig_fetch", "vx_track_rig_pairs",
+    "vx_track_rig_keypoints", "vx_track_rig_matches", "vx_track_rig_layout", "vx_track_rig_block",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -230,6 +232,16 @@ def lib():
         L.vx_track_frame_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.vx_track_frame_matches.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_int32)]
+        L.vx_frame_capture_batch_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.vx_track_rig_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.vx_track_rig_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.vx_track_rig_pairs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_track_rig_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.vx_track_rig_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_int32)]
+        L.vx_track_rig_layout.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.vx_track_rig_block.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int]
         L.vx_cull_default_options.restype = None
         L.vx_cull_default_options.argtypes = [C.c_void_p]
         L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -359,6 +371,35 @@ TRACK_FRAME_RESULT_DTYPE = np.dtype([("path", "<i4"), ("status", "<i4"), ("n_inl
                                      ("parallax", "<f8"), ("pose", "<f8", 7), ("pnp_ran", "<i4"), ("ess_ran", "<i4"),
                                      ("pnp", TRACK_RESULT_DTYPE), ("ess", TRACK_ESS_RESULT_DTYPE)])
 TRACK_PATH_NONE, TRACK_PATH_PNP, TRACK_PATH_ESSENTIAL = range(3)
+
+
+MAX_RIG_CAMERAS = 16  # VX_MAX_RIG_CAMERAS
+
+# vx_rig_camera (include/vx_slam.h): one camera of Context.track_rig_async
+RIG_CAMERA_DTYPE = np.dtype([("last_kf_id", "<u8"), ("last_kf", "<u8"), ("last", "<u8"), ("curr", "<u8"),
+                             ("pose_last7", "<u8"), ("intr4", "<u8")])
+
+
+def rig_camera(curr, intr, last_kf_id=0, last_kf=None, last=None, pose_last=None):
+    """one camera of Context.track_rig_async: Frame handles (last_kf: the frame holding keyframe
+    last_kf_id's features, None: no last keyframe; last: None: the fallback fails), its intrinsics and
+    T_lw of `last` (None: identity)"""
+    return {"last_kf_id": int(last_kf_id), "last_kf": last_kf, "last": last, "curr": curr, "intr": intr,
+            "pose_last": pose_last}
+
+
+def track_rig_layout(cap_pairs0, cap_pairs1, cap_kp):
+    """(cam_offset int64[n], total_bytes) of vx_track_rig_fetch's packed block for these per-camera pair
+    capacities of the two paths and keypoint capacities (vx_track_rig_layout: no context, no device)"""
+    a, b, k = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (cap_pairs0, cap_pairs1, cap_kp))
+    if not (len(a) == len(b) == len(k)):
+        raise ValueError("track_rig_layout: one capacity of each kind per camera")
+    off = np.zeros(max(len(a), 1), np.int64)
+    total = C.c_int64(0)
+    rc = lib().vx_track_rig_layout(len(a), _p(a), _p(b), _p(k), _p(off), C.byref(total))
+    if rc != VX_OK:
+        raise VxError(rc, f"vx_track_rig_layout: {len(a)} cameras / a negative capacity")
+    return off[:len(a)].copy(), int(total.value)
 
 
 def track_frame_options(min_matches=None, min_inliers=None, pnp=None, ess=None):
@@ -809,6 +850,71 @@ class Context:
         d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
         self._check(lib().vx_track_frame_matches(self._h, int(which), C.byref(d), C.byref(n), C.byref(cap)))
         return d.value, n.value, cap.value
+
+    def track_rig_async(self, dmap, cams, opts=None, ratio: float = 0.8):
+        """Tracking::Track for every camera of a rig time step over one map in ONE enqueue
+        (vx_track_rig_async): cams is a list of rig_camera() dicts, opts a track_frame_options() pair
+        serving all of them.  Nothing synchronises; track_rig_fetch() completes it."""
+        po, eo = track_frame_options() if opts is None else opts
+        po = np.ascontiguousarray(po, TRACK_OPTIONS_DTYPE)
+        eo = np.ascontiguousarray(eo, TRACK_ESS_OPTIONS_DTYPE)
+        tab = np.zeros(max(len(cams), 1), RIG_CAMERA_DTYPE)
+        keep = []  # the host arrays the table points to, alive until the call returns
+        hv = lambda f: 0 if f is None else int(f.handle.value or 0)
+        for r, k in zip(tab, cams):
+            intr = np.ascontiguousarray(k["intr"], np.float64)
+            assert intr.size == 4
+            pose = None if k.get("pose_last") is None else np.ascontiguousarray(k["pose_last"], np.float64)
+            assert pose is None or pose.size == 7
+            keep += [intr, pose]
+            r["last_kf_id"], r["last_kf"], r["last"], r["curr"] = k.get("last_kf_id", 0), hv(k.get("last_kf")), hv(k.get("last")), hv(k["curr"])
+            r["intr4"] = intr.ctypes.data
+            r["pose_last7"] = 0 if pose is None else pose.ctypes.data
+        self._check(lib().vx_track_rig_async(self._h, None if dmap is None else dmap.handle, len(cams), _p(tab), ratio,
+                                             _p(po), _p(eo)))
+
+    def track_rig_fetch(self, keypoints: bool = True):
+        """The last track_rig_async in one copy and one synchronisation: per camera the dict
+        track_frame_fetch returns (`result`, `pnp`, `ess`, `keypoints`), sliced out of the packed block
+        at vx_track_rig_layout's offsets."""
+        n = C.c_int(0)
+        self._check(lib().vx_track_rig_fetch(self._h, 1 if keypoints else 0, None, 0, C.byref(n)))
+        b = n.value
+        blk, nbytes = C.c_void_p(), C.c_int64(0)
+        cp0, cp1, ckp = (np.zeros(b, np.int32) for _ in range(3))
+        self._check(lib().vx_track_rig_block(self._h, C.byref(blk), C.byref(nbytes), _p(cp0), _p(cp1), _p(ckp), b))
+        off, total = track_rig_layout(cp0, cp1, ckp)
+        assert total == nbytes.value
+        raw = np.ctypeslib.as_array(C.cast(blk, C.POINTER(C.c_uint8)), shape=(total,))
+        a16 = lambda x: (int(x) + 15) & ~15
+        out = []
+        for i in range(b):
+            o = int(off[i])
+            res = raw[o:o + TRACK_FRAME_RESULT_DTYPE.itemsize].copy().view(TRACK_FRAME_RESULT_DTYPE)[0]
+            o_pm0 = o + a16(TRACK_FRAME_RESULT_DTYPE.itemsize)
+            o_m0 = o_pm0 + a16(cp0[i] * 4)
+            o_pm1 = o_m0 + a16(cp0[i])
+            o_m1 = o_pm1 + a16(cp1[i] * 4)
+            o_kp = o_m1 + a16(cp1[i])
+            k0, k1, nk = int(res["pnp"]["n_pairs"]), int(res["ess"]["n_pairs"]), int(res["n_keypoints"])
+            pairs = [(raw[opm:opm + 4 * k].copy().view(np.int32), raw[om:om + k].copy())
+                     for opm, om, k in ((o_pm0, o_m0, k0), (o_pm1, o_m1, k1))]
+            kp = raw[o_kp:o_kp + nk * KEYPOINT_DTYPE.itemsize].copy().view(KEYPOINT_DTYPE) if keypoints else None
+            out.append({"result": res, "pnp": pairs[0], "ess": pairs[1], "keypoints": kp})
+        return out
+
+    def track_rig_matches(self, cam: int, which: int):
+        """(device pointer of MATCH_DTYPE rows, device pointer of the int32 count, capacity) of camera
+        cam's PnP match (0) or fallback match (1) of the last track_rig_async, as track_frame_matches"""
+        d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._check(lib().vx_track_rig_matches(self._h, int(cam), int(which), C.byref(d), C.byref(n), C.byref(cap)))
+        return d.value, n.value, cap.value
+
+    def frame_capture_batch(self, bank: int, frames):
+        """frames 0 .. len(frames) - 1 of a batch bank (orb_extract_batch*) into the Frame handles in ONE
+        launch (vx_frame_capture_batch_async); no synchronisation"""
+        hs = (C.c_void_p * max(len(frames), 1))(*[f.handle for f in frames])
+        self._check(lib().vx_frame_capture_batch_async(self._h, int(bank), len(frames), hs))
 
     def init_gate_async(self, d_img_ptr: int, w: int, h: int, channels: int, row_stride: int, feats, opts=None,
                         cap_feat: int | None = None):
@@ -1529,6 +1635,32 @@ class DMap:
                                                 C.c_uint64(0 if last_kf_id is None else int(last_kf_id)), _p(mt),
                                                 len(mt), dptr, int(dt), int(rows), int(cols), int(dstride),
                                                 C.c_uint64(int(first_landmark_id)), _p(o), _p(res))
+        return self._create_done(c, rc, res)
+
+    def create_keyframe_frame(self, kf_id, pose7, intr4, frame, *, last_kf_id=None, matches=None, depth=None,
+                              first_landmark_id=0, opts=None, ctx=None):
+        """vx_dmap_create_keyframe_frame: the same over a Frame handle; matches: a device triple
+        (Context.track_frame_matches / track_rig_matches) or None for the context's last match; depth: a
+        host 2-D image or None.  Returns what create_keyframe returns."""
+        c = self.ctx if ctx is None else ctx
+        m_ptr, mn_ptr, m_cap = matches if matches is not None else (None, None, 0)
+        if depth is None:
+            dptr, dt, rows, cols, dstride = None, 0, 0, 0, 0
+        else:
+            depth = np.ascontiguousarray(depth)
+            dptr, dt = C.c_void_p(depth.ctypes.data), DEPTH_TYPES[depth.dtype]
+            rows, cols, dstride = depth.shape[0], depth.shape[1], depth.strides[0]
+        pose = np.ascontiguousarray(pose7, np.float64)
+        intr = None if intr4 is None else np.ascontiguousarray(intr4, np.float64)
+        o = np.ascontiguousarray(keyframe_options() if opts is None else opts, KEYFRAME_OPTIONS_DTYPE)
+        res = np.zeros(1, KEYFRAME_RESULT_DTYPE)
+        rc = lib().vx_dmap_create_keyframe_frame(c.handle, self._h, C.c_uint64(int(kf_id)), _p(pose),
+                                                 None if intr is None else _p(intr), frame.handle,
+                                                 C.c_int(0 if last_kf_id is None else 1),
+                                                 C.c_uint64(0 if last_kf_id is None else int(last_kf_id)),
+                                                 C.c_void_p(m_ptr), C.c_void_p(mn_ptr), C.c_int(int(m_cap)), dptr,
+                                                 C.c_int(int(dt)), C.c_int(int(rows)), C.c_int(int(cols)),
+                                                 C.c_int64(int(dstride)), C.c_uint64(int(first_landmark_id)), _p(o), _p(res))
         return self._create_done(c, rc, res)
 
     def create_results(self):
