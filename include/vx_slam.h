@@ -493,6 +493,15 @@ int vx_sba_plan_factor_work(const vx_sba_plan* plan, int64_t* out4);
 /* The reduced system of the LAST assembly of the last run (S row-major n x n, lower triangle
  * meaningful, damping included; rhs n), for verification against the restatement. */
 int vx_sba_plan_system(vx_ctx* ctx, vx_sba_plan* plan, double* S, double* rhs, int n);
+/* Test hook: the pose step dx (n = 6 n_kf, window order, (upsilon, omega) per keyframe) of the last
+ * iteration of the last run that solved, i.e. the dense pose solve's output.  Sign: S dx = +rhs with
+ * S and rhs as vx_sba_plan_system reports them for the assembly that was factored (rhs = g_T -
+ * sum Y g_p with b = +J^T W e); k_sba_update applies it as T <- exp(dx) T and dp = V^-1 (g_p - W^T dx).
+ * Fixed keyframes keep 0.  Iterations that do not solve (a rejected step's successor, the last one)
+ * leave dx alone, so with max_iterations = 2 it is the solve of the first assembly damped with
+ * lambda_init.  *fail = 1 if a component's Cholesky met a non-positive pivot in any iteration of the
+ * run.  Errors as vx_sba_plan_system (empty plan, wrong n, plan not run). */
+int vx_sba_plan_step(vx_ctx* ctx, vx_sba_plan* plan, double* dx, int n, int32_t* fail);
 /* The same plan from the device-resident map (vx_dmap): window, landmark set and observation set as
  * for the equivalent snapshot, the observation / pair / block tables sorted on the device (two small
  * read-backs: the counts, then the block list for the host's covisibility components and symbolic

@@ -2918,6 +2918,22 @@ int vx_sba_plan_system(vx_ctx* c, vx_sba_plan* p, double* S, double* rhs, int n)
     return VX_OK;
 }
 
+int vx_sba_plan_step(vx_ctx* c, vx_sba_plan* p, double* dx, int n, int32_t* fail) {
+    if (!c || !p || p->c != c || !dx || !fail) return VX_ERR_INVALID;
+    if (p->status != 0) return set_error(c, VX_ERR_STATE, "empty plan");
+    if (n != 6 * p->nk) return set_error(c, VX_ERR_INVALID, "n must be %d", 6 * p->nk);
+    if (!p->ran) return set_error(c, VX_ERR_STATE, "plan not run");
+    SBAState hs;
+    VX_HIP(c, hipMemcpyAsync(dx, p->dx.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipMemcpyAsync(&hs, p->state.p, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    // (fail[it] is rewritten by every iteration that runs: entries past the run's last are not its own)
+    int any = 0;
+    for (int it = 0; it < hs.iterations && it < kSbaMaxIter; ++it) any |= hs.fail[it] != 0;
+    *fail = any;
+    return VX_OK;
+}
+
 int vx_sba_optimize_map(vx_ctx* c, vx_map_view* m, uint64_t ref, int has_ref, const vx_sba_options* opt,
                         vx_sba_stats* st) {
     vx_sba_plan* p = nullptr;

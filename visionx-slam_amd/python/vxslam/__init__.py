@@ -85,7 +85,7 @@ EXPORTS = [
     "vx_ba_plan_run_async", "vx_ba_plan_fetch", "vx_ba_plan_destroy", "vx_ba_plan_info", "vx_ba_plan_layout", "vx_ba_plan_persistent", "vx_ba_plan_fused_tables",
     "vx_ba_plan_inspect", "vx_ba_shard_of", "vx_comm_unique_id", "vx_comm_init", "vx_comm_info", "vx_prof_enable", "vx_prof_count", "vx_prof_name",
     "vx_prof_read", "vx_sba_default_options", "vx_sba_plan_create", "vx_sba_plan_run_async",
-    "vx_sba_plan_fetch", "vx_sba_plan_destroy", "vx_sba_plan_info", "vx_sba_plan_system",
+    "vx_sba_plan_fetch", "vx_sba_plan_destroy", "vx_sba_plan_info", "vx_sba_plan_system", "vx_sba_plan_step",
     "vx_sba_optimize_map", "vx_depth_landmarks", "vx_triangulate", "vx_graph_enable", "vx_graph_counts", "vx_create_ex", "vx_device_cus", "vx_ba_plan_create_ex",
     "vx_dmap_create", "vx_dmap_add_keyframe", "vx_dmap_add_landmarks", "vx_dmap_add_observations",
     "vx_dmap_remove_observations", "vx_dmap_remove_keyframe", "vx_dmap_remove_landmarks", "vx_dmap_set_features",
@@ -1793,6 +1793,15 @@ class SBAPlan:
         rhs = np.zeros(n)
         self.ctx._check(lib().vx_sba_plan_system(self.ctx.handle, self._h, _p(S), _p(rhs), n))
         return S, rhs
+
+    def step(self):
+        """vx_sba_plan_step: (dx, fail) — the pose step of the run's last solving iteration (S dx = rhs;
+        6 per window keyframe, fixed ones 0) and whether any iteration's Cholesky failed."""
+        n = self.info()["n"]
+        dx = np.zeros(n)
+        fail = C.c_int32(0)
+        self.ctx._check(lib().vx_sba_plan_step(self.ctx.handle, self._h, _p(dx), n, C.byref(fail)))
+        return dx, int(fail.value)
 
     def close(self):
         if self._h:
