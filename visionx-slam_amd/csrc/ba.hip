@@ -1215,7 +1215,34 @@ __global__ __launch_bounds__(kFT) void k_ba_iter(BAArgs a, FusedArgs f, int it) 
 //     the granules still missing: re-reading whole rows while the last producers are awaited made
 //     each poll as slow as a full sweep, 0.0503 against 0.0489 ms, r07 — until every tag is the
 //     run's; then the slots are summed in slot order from 0.0 — k_ba_iter's slot combine,
-//     so every run of a plan gives the same bits — and one lane per entry solves the pose;
+//     so every run of a plan gives the same bits — and the entry's 29 sums are staged in LDS;
+//   - behind one workgroup barrier wave 0 solves every entry of the workgroup, lane p the entry
+//     at position p (k_ba_iter's form).  Solved by lane i of each wave for that wave's i-th
+//     entry, a C3 workgroup's 5-8 entries made up to eight waves issue the whole solve_pose
+//     stream for one active lane each, two of them per SIMD; now it is issued once.  Wave 1, on
+//     another SIMD, runs the stop rule beside it.  LDS between the two barriers of phase A
+//     (B1: sums staged, B2: the phase's end):
+//       `terms` as staging: an entry's sums are written by its sweeping wave before B1, read
+//         by wave 0 between B1 and B2 and by nobody else; the landmark stage rewrites `terms`
+//         only behind B2, and its own reads of `terms` end at its closing barrier, before the
+//         next sweep can stage anything;
+//       pose sets: wave 0 reads set (it - 1) & 1 (last written before the previous B2, or in
+//         the prologue) and writes set it & 1 between B1 and B2; every wave has left pose stage
+//         `it` (which reads set (it - 1) & 1) before B1, and set it & 1 is first read behind B2;
+//       s_fault: set by a wave whose sweep ran out before B1, so wave 0, which reads it behind
+//         B1, does not solve from incomplete sums; wave 1 may set it between B1 and B2 (the stop
+//         rule's wait ran out) while wave 0 reads it — either value is fine, the run is void and
+//         every wave leaves behind B2, where all of them read the same value;
+//       s_act: written by wave 1 between B1 and B2, read by every wave behind B2 and not again
+//         after the landmark stage's barriers, which precede the next B1;
+//     every wave executes B1 and B2 once per iteration on every path (a sweep that ran out, a
+//     workgroup without entries, holes, one iteration, an early stop, the test's fault): neither
+//     stands under a condition, and the loop is left only behind B2 on workgroup-wide values.
+//     Between B1 and B2 every thread also requests what the landmark stage reads first (its
+//     observation record, its landmark's position in lpos, its run): loop-invariant or written
+//     only inside the landmark stage, whose closing barrier precedes B1, and next written behind
+//     B2.  (In place of B1, a generation word per wave in LDS that wave 0 polls measured slower:
+//     LocalBA alone 0.0472-0.0475 against 0.0467-0.0468 ms, r15);
 //   - the tag is the run's generation + 1 (w.gen, on the device: graph replays see it), never 0.
 //     Granules are per iteration (no reuse inside a run) and runs of one plan are stream-ordered, so
 //     a granule with this run's tag was written in this run for this iteration; whatever an earlier
@@ -1293,7 +1320,7 @@ __device__ __forceinline__ bool win_spin_fail(int& k, long long t0, int* fault) 
     return false;
 }
 
-// (239 VGPRs, no scratch, two waves per SIMD.  Sized for three — 168 VGPRs, so that a third wave of
+// (238 VGPRs, no scratch, two waves per SIMD.  Sized for three — 168 VGPRs, so that a third wave of
 // the other streams' kernels fits beside it — it spills outside the observation rounds: LocalBA
 // alone 0.067 against 0.054 ms, the C3 pipeline 0.074 against 0.063 ms/frame, r06i)
 template <int kFT>
@@ -1530,9 +1557,10 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
         double* const kslot = ks0 + (it & 1) * kFK * kLdsStride;
         const double* const kprev = ks0 + ((it + 1) & 1) * kFK * kLdsStride;
         // ---- A: every wave sweeps the partial slots of its entries' rows (entries dealt as in the
-        // pose stage), sums them in slot order and solves its entries; wave 1 also decides whether
-        // iteration it runs (the stop rule of it - 1: its granules have had an iteration to arrive
-        // and are requested ahead of the wave's own sweep)
+        // pose stage), sums them in slot order and stages the sums; behind a barrier wave 0 solves
+        // every entry while wave 1 (another SIMD) decides whether iteration it runs (the stop rule of
+        // it - 1: its granules have had an iteration to arrive and are requested ahead of the wave's
+        // own sweep)
         wgran dgr[4] = {0, 0, 0, 0};
         if (wv == 1 && it > 0) decide_issue(it - 1, dgr);
         {
@@ -1599,31 +1627,44 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
                     st_gran2(w.stop + ((size_t)it * nk + erow) * 4 + (lane - 27) * 2, acc, tag);
             }
             __builtin_amdgcn_s_setprio(3);
-#ifndef VX_WIN_TRACE_LM
+#if !defined(VX_WIN_TRACE_LM) && !defined(VX_WIN_TRACE_SOLVE)
             if (wv == 0 && it < 5) VX_KT(1 + 3 * it);
 #endif
             if (!okw && lane == 0) s_fault = 1;
-            // (the wave's own LDS stores, read back by its own lanes: LDS keeps a wave's order)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int js = wv + kFW * lane;  // lane i solves the wave's i-th entry
-            if (okw && js < n_ent && s_ke[js < kFK ? js : 0].x >= 0) {
-                double S[kNTerms];
-#pragma unroll
-                for (int q = 0; q < kNTerms; ++q) S[q] = stage[js * kWinSStride + q];
-                double* sl = kslot + js * kLdsStride;
-                const double* sp = kprev + js * kLdsStride;
-                double T[8], Rm[9];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) T[j] = sp[j];
-                solve_pose(a, (int)sp[21], S, T, Rm);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) sl[j] = T[j];
-#pragma unroll
-                for (int j = 0; j < 9; ++j) sl[8 + j] = Rm[j];
-            }
         }
+        // ---- every wave's sums are staged (and a sweep that ran out has set s_fault): wave 0 solves,
+        // lane p the entry at position p, as k_ba_iter does — one solve_pose stream per workgroup on
+        // one SIMD, not one per wave for a single lane each
+        __syncthreads();
+#ifdef VX_WIN_TRACE_SOLVE  // (trace variant: slot 1 + 3 it = every wave's sums staged, 3 + 3 it = solve done)
+        if (wv == 0 && it < 5) VX_KT(1 + 3 * it);
+#endif
+        // the landmark stage's first two LDS levels do not depend on the new poses (lpos is written
+        // only inside the landmark stage, behind barriers of its own): requested here, so that the
+        // waves that wait for wave 0's solve have them when the barrier opens
+        const int4 orec = s_orec[tid];
+        const double2 ouv = s_ouv[tid];
+        const D3 PO{lpos[3 * orec.y], lpos[3 * orec.y + 1], lpos[3 * orec.y + 2]};
+        const int r0 = s_run[3 * tid], r1 = s_run[3 * tid + 1], lslot = s_run[3 * tid + 2];
+        if (tid < kFK && ke.x >= 0 && !s_fault) {
+            const double* const stage = terms;
+            double S[kNTerms];
+#pragma unroll
+            for (int q = 0; q < kNTerms; ++q) S[q] = stage[tid * kWinSStride + q];
+            double* sl = kslot + tid * kLdsStride;
+            const double* sp = kprev + tid * kLdsStride;
+            double T[8], Rm[9];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) T[j] = sp[j];
+            solve_pose(a, (int)sp[21], S, T, Rm);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sl[j] = T[j];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) sl[8 + j] = Rm[j];
+        }
+#ifdef VX_WIN_TRACE_SOLVE
+        if (wv == 0 && it < 4) VX_KT(3 + 3 * it);
+#endif
         if (wv == 1) {
             __builtin_amdgcn_s_setprio(0);  // (a polling wave leaves the SIMD to co-resident waves)
             const int act = it == 0 ? (b == 0 ? hello_sweep() : 1) : decide(it - 1, dgr);
@@ -1646,9 +1687,6 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
         // ---- landmark stage of iteration it (local_ba.cpp:176-238), as k_ba_iter
         {
             double h[9];
-            const int4 orec = s_orec[tid];
-            const double2 ouv = s_ouv[tid];
-            const D3 PO{lpos[3 * orec.y], lpos[3 * orec.y + 1], lpos[3 * orec.y + 2]};
             const bool ok = obs_terms<true>(a, PO, orec.x, ouv, kslot, kLdsStride, kslot + 8, kLdsStride, kslot + 17,
                                             kLdsStride, h);
 #pragma unroll
@@ -1658,8 +1696,6 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
             if (own) {
                 double hs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
                 int obs = 0;
-                const int r0 = s_run[3 * tid], r1 = s_run[3 * tid + 1];
-                int lslot = s_run[3 * tid + 2];
                 const D3 P0{lpos[3 * tid], lpos[3 * tid + 1], lpos[3 * tid + 2]};
                 for (int q = r0; q < r1; ++q) {
 #pragma unroll
@@ -1677,7 +1713,9 @@ __global__ __launch_bounds__(kFT) void k_ba_win(BAArgs a, FusedArgs f, WinArgs w
         if (wv == 0 && it < 5) VX_KT(1 + 3 * it);
 #endif
         if (it + 1 < M) pose_stage(it + 1);
+#ifndef VX_WIN_TRACE_SOLVE
         if (wv == 0 && it < 4) VX_KT(3 + 3 * it);
+#endif
     }
     // ---- the last iteration's statistics (a stop inside the loop wrote them), then the next run's
     // generation: workgroup 0's wave 1 swept hello[] in iteration 0, so every workgroup has read
