@@ -26,6 +26,8 @@ constexpr int kQB = 256;      // queries per block (one per thread)
 constexpr int kTC = 64;       // train rows per chunk
 constexpr int kMergeBlock = 1024;
 constexpr int kMergeBatch = 32;   // chunk partials in flight per thread in k_knn_merge
+constexpr int kMaxChunksY = 32768;  // chunks per k_knn_partial launch (grid.y: 2^22 rows are 65536 chunks, past the
+                                    // 65535 a grid's y may be relied on to take)
 constexpr int kMergeQB = 64;      // queries per k_knn_merge workgroup (one wave: more CUs, same loads)
 constexpr unsigned kNone = 0xffffffffu;
 
@@ -33,12 +35,12 @@ __global__ __launch_bounds__(kQB) void k_knn_partial(const uint8_t* __restrict__
                                                      const int* __restrict__ nq_p, int nq_host,
                                                      const uint8_t* __restrict__ t,
                                                      const int* __restrict__ nt_p, int nt_host,
-                                                     int n_chunks_cap, uint2* __restrict__ partial,
+                                                     int chunk0, uint2* __restrict__ partial,
                                                      int q_stride) {
     __shared__ uint4 st[kTC * 2];
     const int nq = nq_p ? min(*nq_p, nq_host) : nq_host;  // device count clamped to capacity
     const int nt = nt_p ? min(*nt_p, nt_host) : nt_host;
-    const int chunk = blockIdx.y;
+    const int chunk = chunk0 + blockIdx.y;  // (a launch takes up to kMaxChunksY chunks from chunk0 on)
     const int t0 = chunk * kTC;
     const int qi = blockIdx.x * kQB + threadIdx.x;
     if (blockIdx.x * kQB >= nq || t0 >= nt) return;  // block-uniform
@@ -66,7 +68,6 @@ __global__ __launch_bounds__(kQB) void k_knn_partial(const uint8_t* __restrict__
         k1 = min(k1, key);
     }
     partial[(long long)chunk * q_stride + qi] = make_uint2(k1, k2);
-    (void)n_chunks_cap;
 }
 
 // Whole-row kNN-2 (default): a workgroup takes kRQ queries against the whole train set, so no
@@ -387,12 +388,15 @@ int match_enqueue_to(vx_ctx* c, const uint8_t* dq, const int* dnq, int nq_host, 
         VX_LAUNCH_CHECK(c, "k_knn_compact");
         return VX_OK;
     }
-    VX_HIP(c, launch(c, kStMatchPartial, k_knn_partial, dim3((q_cap + kQB - 1) / kQB, n_chunks), dim3(kQB), 0,
-                     c->stream, dq, dnq, nq_host, dt, dnt, nt_host, n_chunks, c->partial.as<uint2>(), q_stride));
+    // (an empty capacity still launches one workgroup, which reads the count and leaves)
+    for (int c0 = 0; c0 < std::max(n_chunks, 1); c0 += kMaxChunksY)
+        VX_HIP(c, launch(c, kStMatchPartial, k_knn_partial,
+                         dim3(std::max((q_cap + kQB - 1) / kQB, 1), std::max(std::min(n_chunks - c0, kMaxChunksY), 1)),
+                         dim3(kQB), 0, c->stream, dq, dnq, nq_host, dt, dnt, nt_host, c0, c->partial.as<uint2>(), q_stride));
     {
         ProfScope ps(c, kStMatchMerge);
         unsigned* best = reinterpret_cast<unsigned*>(c->partial.as<uint2>() + (size_t)n_chunks * q_stride);
-        hipLaunchKernelGGL(k_knn_merge, dim3((q_cap + kMergeQB - 1) / kMergeQB), dim3(kMergeQB), 0, c->stream, c->partial.as<uint2>(),
+        hipLaunchKernelGGL(k_knn_merge, dim3(std::max((q_cap + kMergeQB - 1) / kMergeQB, 1)), dim3(kMergeQB), 0, c->stream, c->partial.as<uint2>(),
                            dnq, nq_host, dnt, nt_host, q_stride, ratio, best);
         VX_LAUNCH_CHECK(c, "k_knn_merge");
         hipLaunchKernelGGL(k_knn_compact, dim3(1), dim3(kMergeBlock), 0, c->stream, best, dnq, nq_host,

@@ -167,6 +167,8 @@ def lib():
                                            C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
                                            C.c_float]
         L.vx_match_batch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.vx_match_knn2_ratio_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p,
+                                                C.POINTER(C.c_void_p), C.c_void_p, C.c_float]
         L.vx_prof_name.restype = C.c_char_p
         L.vx_ba_plan_destroy.argtypes = [C.c_void_p]
         L.vx_dmap_destroy.argtypes = [C.c_void_p]
@@ -983,6 +985,18 @@ class Context:
         n = C.c_int(0)
         self._check(lib().vx_match_batch_fetch(self._h, pair, _p(out), cap, C.byref(n)))
         return out[:n.value].copy()
+
+    def match_batch(self, pairs, ratio: float = 0.8):
+        """vx_match_knn2_ratio_batch: pairs is a list of (query, train) host descriptor arrays (either may be
+        empty), matched in one batched call; returns one match array per pair."""
+        n = len(pairs)
+        qs = [np.ascontiguousarray(q, np.uint8).reshape(-1, 32) for q, _ in pairs]
+        ts = [np.ascontiguousarray(t, np.uint8).reshape(-1, 32) for _, t in pairs]
+        ptrs = lambda xs: (C.c_void_p * max(n, 1))(*[C.c_void_p(x.ctypes.data if len(x) else None) for x in xs])
+        nq = np.array([len(q) for q in qs], np.int32)
+        nt = np.array([len(t) for t in ts], np.int32)
+        self._check(lib().vx_match_knn2_ratio_batch(self._h, n, ptrs(qs), _p(nq), ptrs(ts), _p(nt), C.c_float(ratio)))
+        return [self.match_batch_fetch(i, max(len(q), 1)) for i, q in enumerate(qs)]
 
     def match_fetch(self, cap: int = 8192):
         out = np.zeros(cap, MATCH_DTYPE)
