@@ -44,6 +44,7 @@
  *   vx_dmap_create_keyframe* <- Tracking::CreateKeyFrame's insertion: CreateLandmarksFromDepth,
  *                            TriangulateWithLastKeyFrame, Map::InsertKeyFrame on the resident map
  *                                                                core/frontend/tracking.cpp:577-584
+ *   vx_dmap_create_keyframes_rig <- the same for every camera of a rig time step in one call
  *   vx_ba_plan_create_dmap <- the gather of local_ba.cpp:42-108 from the resident map
  *   vx_sba_*              (no reference counterpart: north_star's Schur-complement dense solve)
  *
@@ -1175,6 +1176,47 @@ int vx_track_rig_layout(int n_cams, const int32_t* cap_pairs0, const int32_t* ca
  * vx_track_rig_layout.  VX_ERR_STATE before a fetch. */
 int vx_track_rig_block(vx_ctx* ctx, const uint8_t** block, int64_t* bytes, int32_t* cap_pairs0, int32_t* cap_pairs1,
                        int32_t* cap_kp, int cap_cams);
+
+/* ---------------------------------------------------------------- CreateKeyFrame for a rig (keyframe_rig.hip)
+ * <- Tracking::CreateKeyFrame (tracking.cpp:577-584) for every camera of a rig time step that inserts a
+ *    keyframe, over one shared map: ONE upload (argument table + all depth images), one memset, four
+ *    launches (k_rig_kf_feat -> k_rig_kf_match -> k_rig_kf_count -> k_rig_kf_commit) and ONE
+ *    synchronisation whatever the number of cameras.  The map, the results and the records are those of
+ *    n_cams vx_dmap_create_keyframe_frame calls in camera order: camera i + 1's first_landmark_id is
+ *    camera i's next_landmark_id, its rows follow camera i's.
+ *
+ *    All or nothing: when any camera's error word is set nothing is committed, every results[i]
+ *    carries its own error_bits (0 for a camera without a fault) and the call returns VX_ERR_INVALID.
+ *    Besides the single call's refusals, checked per camera, the call refuses what would make the
+ *    cameras depend on one another: a kf_id or a last_kf_id named by two cameras (VX_KF_ERR_RIG_REPEAT
+ *    on each of them), and a last_kf_id that is not live BEFORE the call, another camera's new kf_id
+ *    included (VX_KF_ERR_NO_LAST).  The id range checked against the map is the call's,
+ *    [first_landmark_id, first_landmark_id + the sum of the frames' capacities): VX_KF_ERR_ID_RANGE is
+ *    set on every camera.  A has_last camera without a device match list is VX_ERR_INVALID (no bits). */
+/* the rig call's own bit, 64, after the six of vx_keyframe_result above */
+#define VX_KF_ERR_RIG_REPEAT (1 << 6) /* this camera's kf_id or last_kf_id is named by another camera of the call */
+typedef struct {
+    uint64_t kf_id;                      /* the new keyframe */
+    const double* pose7;                 /* host: x y z w | t, T_cw */
+    const double* intr4;                 /* host */
+    const vx_frame* curr;                /* its resident frame */
+    int32_t has_last;
+    uint64_t last_kf_id;                 /* a live keyframe of the map no other camera of the call names */
+    const vx_match* d_matches;           /* device (vx_track_rig_matches(cam, 0)); required when has_last */
+    const int32_t* d_n_matches;
+    int32_t cap_matches;
+    const void* depth;                   /* HOST image, NULL = empty (Depth().empty(), tracking.cpp:591-594) */
+    int32_t depth_type, rows, cols;
+    int64_t row_stride;
+} vx_rig_keyframe;
+/* n_cams in [1, VX_MAX_RIG_CAMERAS]: the cameras that create a keyframe this step.  results: n_cams
+ * records.  vx_dmap_create_results afterwards returns all cameras' records concatenated in camera order
+ * (creation order); camera i's slice follows from the results' counts.  A context other than the map's
+ * waits for the map's stream first.  May block at its start until the previous create call's upload has
+ * left the pinned staging it reuses. */
+int vx_dmap_create_keyframes_rig(vx_ctx* ctx, vx_dmap* map, int n_cams, const vx_rig_keyframe* cams,
+                                 uint64_t first_landmark_id, const vx_keyframe_options* opt,
+                                 vx_keyframe_result* results);
 
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,

@@ -40,275 +40,31 @@
 // rejected call leaves the map as it was.  The arrays are grown for the worst case before the
 // launches (cap_feat landmarks, 2 cap_feat observations: a feature is linked at most once), so the
 // device sequence needs no count from the host.
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstring>
-
-#include "vx_internal.hpp"
-#include "dmap.hpp"
-#include "lm_math.hpp"
+//
+// The kernels' program text lives in keyframe_bodies.hpp, shared with the rig form (keyframe_rig.hip).
+#include "keyframe_bodies.hpp"
 
 namespace vx {
 namespace {
 
-using namespace vx::lm;
-
-constexpr int kThreads = 256;
-constexpr int kBlock = 1024;
-constexpr int kWaves = kBlock / 64;
-
-struct KfArgs {
-    // the new keyframe
-    uint64_t kf_id, last_kf_id, first_id;
-    const uint8_t* xy;       // position rows: two floats (or doubles, xy_f64) at xy + i * stride
-    int64_t stride;
-    int xy_f64;
-    const int* n_feat;
-    int cap_feat;
-    int has_depth;
-    DepthView dv;            // depth image + the new keyframe's intrinsics and T_cw
-    // the last keyframe (rows of the map)
-    int has_last, k_last, nf_last;
-    int64_t f0_last;
-    const vx_match* m;
-    const int* n_matches;
-    int cap_matches;
-    double min_angle_rad, max_err;
-    // the map: arrays and the used counts the new rows follow
-    double *kf_pose, *kf_intr, *feat_uv;
-    uint64_t* feat_lm;
-    uint8_t* feat_fl;
-    uint64_t* lm_id;
-    double* lm_pos;
-    uint8_t* lm_bad;
-    int* obs_lm;
-    uint64_t *obs_kf, *obs_fi;
-    int64_t *obs_id, *id_row;
-    int k_new;
-    int64_t f0, n_lm0, n_obs0, n_ids0;
-    double pose[7], intr[4];
-    // scratch
-    int* dvalid;             // per feature: CreateLandmarksFromDepth made a landmark
-    double* dpw;
-    int* tvalid;             // per match: passed the triangulation gate
-    double* tpw;
-    int *winner, *qseen, *err;
-    // host-pinned outputs
-    vx_keyframe_result* hdr;
-    vx_keyframe_landmark* rec;
-};
-
-__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
+using namespace vx::kf;
 
 __global__ __launch_bounds__(kThreads) void k_kf_feat(KfArgs a) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    const int n = clampi(*a.n_feat, a.cap_feat);
-    if (i >= n) return;
-    const uint8_t* p = a.xy + (int64_t)i * a.stride;
-    double x, y;
-    if (a.xy_f64) {
-        x = reinterpret_cast<const double*>(p)[0];
-        y = reinterpret_cast<const double*>(p)[1];
-    } else {  // Feature::position from cv::KeyPoint::pt: float -> double, exact
-        x = (double)reinterpret_cast<const float*>(p)[0];
-        y = (double)reinterpret_cast<const float*>(p)[1];
-    }
-    const int64_t g = a.f0 + i;
-    a.feat_uv[2 * g] = x;
-    a.feat_uv[2 * g + 1] = y;
-    a.feat_lm[g] = 0;  // the frame arrives without links (tracking.cpp:577)
-    a.feat_fl[g] = 0;
-    a.winner[i] = INT_MAX;
-    int ok = 0;
-    if (a.has_depth) {
-        D3 pw;
-        if (depth_point(a.dv, x, y, pw)) {
-            a.dpw[3 * i] = pw.x;
-            a.dpw[3 * i + 1] = pw.y;
-            a.dpw[3 * i + 2] = pw.z;
-            ok = 1;
-        }
-    }
-    a.dvalid[i] = ok;
+    feat_body(a, OwnBase{a}, blockIdx.x * kThreads + threadIdx.x);
 }
 
 __global__ __launch_bounds__(kThreads) void k_kf_match(KfArgs a) {
-    const int k = blockIdx.x * kThreads + threadIdx.x;
-    const int n = clampi(*a.n_matches, a.cap_matches);
-    if (k >= n) return;
-    a.tvalid[k] = 0;
-    const int n2 = clampi(*a.n_feat, a.cap_feat);
-    const vx_match mt = a.m[k];
-    const int qi = mt.query_idx, ti = mt.train_idx;
-    if (qi < 0 || qi >= a.nf_last || ti < 0 || ti >= n2) {
-        atomicOr(a.err, VX_KF_ERR_MATCH_RANGE);
-        return;
-    }
-    if (atomicAdd(&a.qseen[qi], 1) != 0) atomicOr(a.err, VX_KF_ERR_DUP_QUERY);
-    const int64_t g1 = a.f0_last + qi, g2 = a.f0 + ti;
-    // has_landmark of the last keyframe's feature; of the new one: only the depth loop set any
-    if ((a.feat_fl[g1] & 1) || a.dvalid[ti]) return;
-    const double x1 = a.feat_uv[2 * g1], y1 = a.feat_uv[2 * g1 + 1];
-    const double x2 = a.feat_uv[2 * g2], y2 = a.feat_uv[2 * g2 + 1];
-    Pose T1;
-    double c1[4];
-    for (int j = 0; j < 4; ++j) T1.q[j] = a.kf_pose[7 * (int64_t)a.k_last + j];
-    for (int j = 0; j < 3; ++j) T1.t[j] = a.kf_pose[7 * (int64_t)a.k_last + 4 + j];
-    for (int j = 0; j < 4; ++j) c1[j] = a.kf_intr[4 * (int64_t)a.k_last + j];
-    D3 pw;
-    if (!tri_gate(x1, y1, x2, y2, c1, a.intr, T1, a.dv.T, a.min_angle_rad, a.max_err, pw)) return;
-    a.tvalid[k] = 1;
-    a.tpw[3 * k] = pw.x;
-    a.tpw[3 * k + 1] = pw.y;
-    a.tpw[3 * k + 2] = pw.z;
-    atomicMin(&a.winner[ti], k);
-}
-
-// Exclusive rank of this thread's flag among the block's flags (thread order) and their total.
-// Two barriers: the wave counts are read by everyone before the next call rewrites them.
-__device__ __forceinline__ int block_rank(bool flag, int* s_cnt, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t b = __ballot(flag);
-    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-    if (lane == 0) s_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const int v = s_cnt[w];
-        before += w < wave ? v : 0;
-        all += v;
-    }
-    __syncthreads();
-    *total = all;
-    return before + in_wave;
-}
-
-__device__ __forceinline__ void put_obs(const KfArgs& a, int64_t j, int row, uint64_t kf, uint64_t fi) {
-    const int64_t o = a.n_obs0 + j, id = a.n_ids0 + j;
-    a.obs_lm[o] = row;
-    a.obs_kf[o] = kf;
-    a.obs_fi[o] = fi;
-    a.obs_id[o] = id;
-    a.id_row[id] = o;
-}
-
-__device__ __forceinline__ void put_landmark(const KfArgs& a, int j, int kind, int feat_curr, int feat_last,
-                                             const double* pw) {
-    const int64_t row = a.n_lm0 + j;
-    const uint64_t id = a.first_id + (uint64_t)j;
-    a.lm_id[row] = id;
-    a.lm_pos[3 * row] = pw[0];
-    a.lm_pos[3 * row + 1] = pw[1];
-    a.lm_pos[3 * row + 2] = pw[2];
-    a.lm_bad[row] = 0;
-    a.feat_lm[a.f0 + feat_curr] = id;
-    a.feat_fl[a.f0 + feat_curr] = 1;  // has_landmark, not outlier
-    vx_keyframe_landmark r;
-    r.lm_id = id;
-    r.row = (int)row;
-    r.kind = kind;
-    r.feat_curr = feat_curr;
-    r.feat_last = feat_last;
-    r.pw[0] = pw[0];
-    r.pw[1] = pw[1];
-    r.pw[2] = pw[2];
-    a.rec[j] = r;
+    match_body(a, OwnBase{a}, blockIdx.x * kThreads + threadIdx.x);
 }
 
 __global__ void __launch_bounds__(kBlock) k_kf_commit(KfArgs a) {
     __shared__ int s_cnt[kWaves];
-    const int tid = threadIdx.x;
-    const int nf = clampi(*a.n_feat, a.cap_feat);
-    const int nm = a.has_last ? clampi(*a.n_matches, a.cap_matches) : 0;
-    const int err = *a.err;
-    if (err) {  // validate-then-commit: a rejected call writes the header only
-        if (tid == 0) {
-            vx_keyframe_result h{};
-            h.n_feat = nf;
-            h.n_matches = nm;
-            h.first_landmark_id = h.next_landmark_id = a.first_id;
-            h.error_bits = err;
-            *a.hdr = h;
-        }
-        return;
-    }
-    // 1: CreateLandmarksFromDepth's landmarks, feature order
-    int nd = 0;
-    for (int base = 0; base < nf; base += kBlock) {
-        const int i = base + tid;
-        const bool made = i < nf && a.dvalid[i] != 0;
-        int total;
-        const int r = block_rank(made, s_cnt, &total);
-        if (made) {
-            const int j = nd + r;
-            put_landmark(a, j, 0, i, -1, a.dpw + 3 * (int64_t)i);
-            put_obs(a, j, (int)(a.n_lm0 + j), a.kf_id, (uint64_t)i);
-        }
-        nd += total;
-    }
-    // 2: TriangulateWithLastKeyFrame's, match order; a train feature's first passing match wins
-    int nt = 0;
-    for (int base = 0; base < nm; base += kBlock) {
-        const int k = base + tid;
-        bool made = false;
-        vx_match mt{};
-        if (k < nm && a.tvalid[k]) {  // (tvalid: both indices are in range)
-            mt = a.m[k];
-            made = a.winner[mt.train_idx] == k;
-        }
-        int total;
-        const int r = block_rank(made, s_cnt, &total);
-        if (made) {
-            const int j = nd + nt + r;
-            const int64_t o = (int64_t)nd + 2 * (int64_t)(nt + r);
-            const uint64_t id = a.first_id + (uint64_t)j;
-            put_landmark(a, j, 1, mt.train_idx, mt.query_idx, a.tpw + 3 * (int64_t)k);
-            put_obs(a, o, (int)(a.n_lm0 + j), a.last_kf_id, (uint64_t)mt.query_idx);  // (tracking.cpp:916)
-            put_obs(a, o + 1, (int)(a.n_lm0 + j), a.kf_id, (uint64_t)mt.train_idx);   // (:917)
-            a.feat_lm[a.f0_last + mt.query_idx] = id;
-            a.feat_fl[a.f0_last + mt.query_idx] = 1;
-        }
-        nt += total;
-    }
-    if (tid == 0) {  // Map::InsertKeyFrame's rows and the header
-        for (int j = 0; j < 7; ++j) a.kf_pose[7 * (int64_t)a.k_new + j] = a.pose[j];
-        for (int j = 0; j < 4; ++j) a.kf_intr[4 * (int64_t)a.k_new + j] = a.intr[j];
-        vx_keyframe_result h{};
-        h.n_feat = nf;
-        h.n_depth = nd;
-        h.n_triangulated = nt;
-        h.n_matches = nm;
-        h.first_landmark_id = a.first_id;
-        h.next_landmark_id = a.first_id + (uint64_t)(nd + nt);
-        *a.hdr = h;
-    }
+    const OwnBase b{a};
+#define KF_REJECTED(err) ((err) != 0)
+#include "keyframe_commit_body.inc"
+#undef KF_REJECTED
 }
 
-// room for `want` bytes keeping the first `used` (doubling, as the map's edit calls grow); the copy
-// runs on the map context's stream, and no stream may still use the old block when it is freed
-int grow(vx_ctx* c, vx_dmap* m, DevBuf& d, size_t used, size_t want) {
-    if (want <= d.bytes) return VX_OK;
-    size_t cap = std::max<size_t>(d.bytes * 2, 4096);
-    while (cap < want) cap *= 2;
-    void* np = nullptr;
-    VX_HIP(c, hipMalloc(&np, cap));
-    hipError_t e = hipSuccess;
-    if (used) e = hipMemcpyAsync(np, d.p, used, hipMemcpyDeviceToDevice, m->c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->c->stream);
-    if (e == hipSuccess && c != m->c) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(np);
-        return hip_fail(c, e, "growing a map array");
-    }
-    d.release();
-    d.p = np;
-    d.bytes = cap;
-    return VX_OK;
-}
-
-size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 constexpr size_t kRecOff = 64;  // pinned block: vx_keyframe_result | records
 
 int reject(vx_ctx* c, vx_keyframe_result* res, int bits, const char* what) {
@@ -329,8 +85,6 @@ struct Input {
     int depth_type, rows, cols;
     int64_t row_stride;
 };
-
-int depth_elem(int type) { return type == VX_DEPTH_U16 ? 2 : (type == VX_DEPTH_F32 ? 4 : 8); }
 
 // the sequence over inputs already on the device, its one synchronisation, then the host mirrors
 int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4, const Input& in,
@@ -357,34 +111,16 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     if (bits & VX_KF_ERR_NO_CAMERA) return reject(c, res, bits, "a keyframe without a camera");
     if (bits) return reject(c, res, bits, "a landmark id of the range is already in the map");
     const bool has_depth = in.depth && in.rows > 0 && in.cols > 0;  // Depth().empty() (tracking.cpp:591-594)
-    if (has_depth) {
-        if (in.depth_type < VX_DEPTH_U16 || in.depth_type > VX_DEPTH_F64)
-            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", in.depth_type);
-        if (in.row_stride < (int64_t)in.cols * depth_elem(in.depth_type))
-            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
-    }
+    int rc;
+    if (has_depth && (rc = check_depth(c, in.depth_type, in.cols, in.row_stride))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     const int64_t k = (int64_t)m->kf_id.size(), f0 = m->kf_feat_ptr.back();
     const int64_t f0_last = has_last ? m->kf_feat_ptr[k_last] : 0;
     const int nf_last = has_last ? (int)(m->kf_feat_ptr[k_last + 1] - f0_last) : 0;
     if (m->n_lm + cap_feat > (int64_t)INT_MAX || f0 + cap_feat > (int64_t)INT_MAX)
         return set_error(c, VX_ERR_CAPACITY, "the map's rows would pass 2^31");
-    // the worst case: every feature linked, every link a triangulated landmark's (two observations)
-    int rc;
     const size_t cf = (size_t)cap_feat;
-    if ((rc = grow(c, m, m->kf_pose, (size_t)k * 56, (size_t)(k + 1) * 56))) return rc;
-    if ((rc = grow(c, m, m->kf_intr, (size_t)k * 32, (size_t)(k + 1) * 32))) return rc;
-    if ((rc = grow(c, m, m->feat_uv, (size_t)f0 * 16, ((size_t)f0 + cf) * 16))) return rc;
-    if ((rc = grow(c, m, m->feat_lm, (size_t)f0 * 8, ((size_t)f0 + cf) * 8))) return rc;
-    if ((rc = grow(c, m, m->feat_fl, (size_t)f0, (size_t)f0 + cf))) return rc;
-    if ((rc = grow(c, m, m->lm_id, (size_t)m->n_lm * 8, ((size_t)m->n_lm + cf) * 8))) return rc;
-    if ((rc = grow(c, m, m->lm_pos, (size_t)m->n_lm * 24, ((size_t)m->n_lm + cf) * 24))) return rc;
-    if ((rc = grow(c, m, m->lm_bad, (size_t)m->n_lm, (size_t)m->n_lm + cf))) return rc;
-    if ((rc = grow(c, m, m->obs_lm, (size_t)m->n_obs * 4, ((size_t)m->n_obs + 2 * cf) * 4))) return rc;
-    if ((rc = grow(c, m, m->obs_kf, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
-    if ((rc = grow(c, m, m->obs_fi, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
-    if ((rc = grow(c, m, m->obs_id, (size_t)m->n_obs * 8, ((size_t)m->n_obs + 2 * cf) * 8))) return rc;
-    if ((rc = grow(c, m, m->id_row, (size_t)m->n_ids * 8, ((size_t)m->n_ids + 2 * cf) * 8))) return rc;
+    if ((rc = grow_map(c, m, 1, cf))) return rc;
     VX_HIP(c, K.dvalid.ensure(std::max<size_t>(cf, 1) * sizeof(int)));
     VX_HIP(c, K.dpw.ensure(std::max<size_t>(cf, 1) * 3 * sizeof(double)));
     VX_HIP(c, K.tvalid.ensure((size_t)std::max(cap_m, 1) * sizeof(int)));
@@ -396,7 +132,6 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     KfArgs a{};
     a.kf_id = kf_id;
     a.last_kf_id = last_kf_id;
-    a.first_id = first_id;
     a.xy = in.xy;
     a.stride = in.stride;
     a.xy_f64 = in.xy_f64;
@@ -408,12 +143,7 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     a.dv.rows = in.rows;
     a.dv.cols = in.cols;
     a.dv.stride = in.row_stride;
-    a.dv.fx = intr4[0];
-    a.dv.fy = intr4[1];
-    a.dv.cx = intr4[2];
-    a.dv.cy = intr4[3];
-    for (int j = 0; j < 4; ++j) a.dv.T.q[j] = pose7[j];
-    for (int j = 0; j < 3; ++j) a.dv.T.t[j] = pose7[4 + j];
+    camera_args(a, pose7, intr4, opt);
     a.has_last = has_last ? 1 : 0;
     a.k_last = k_last;
     a.nf_last = nf_last;
@@ -421,28 +151,13 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     a.m = in.matches;
     a.n_matches = in.n_matches;
     a.cap_matches = cap_m;
-    a.min_angle_rad = opt->tri_min_angle_deg * M_PI / 180.0;  // tracking.cpp:870-871
-    a.max_err = opt->tri_max_reproj_error;
-    a.kf_pose = m->kf_pose.as<double>();
-    a.kf_intr = m->kf_intr.as<double>();
-    a.feat_uv = m->feat_uv.as<double>();
-    a.feat_lm = m->feat_lm.as<uint64_t>();
-    a.feat_fl = m->feat_fl.as<uint8_t>();
-    a.lm_id = m->lm_id.as<uint64_t>();
-    a.lm_pos = m->lm_pos.as<double>();
-    a.lm_bad = m->lm_bad.as<uint8_t>();
-    a.obs_lm = m->obs_lm.as<int>();
-    a.obs_kf = m->obs_kf.as<uint64_t>();
-    a.obs_fi = m->obs_fi.as<uint64_t>();
-    a.obs_id = m->obs_id.as<int64_t>();
-    a.id_row = m->id_row.as<int64_t>();
+    map_pointers(a, m);
     a.k_new = (int)k;
     a.f0 = f0;
     a.n_lm0 = m->n_lm;
     a.n_obs0 = m->n_obs;
     a.n_ids0 = m->n_ids;
-    for (int j = 0; j < 7; ++j) a.pose[j] = pose7[j];
-    for (int j = 0; j < 4; ++j) a.intr[j] = intr4[j];
+    a.first_id = first_id;
     a.dvalid = K.dvalid.as<int>();
     a.dpw = K.dpw.as<double>();
     a.tvalid = K.tvalid.as<int>();
@@ -469,53 +184,18 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
         if (res->error_bits & VX_KF_ERR_MATCH_RANGE) return set_error(c, VX_ERR_INVALID, "match index out of range");
         return set_error(c, VX_ERR_INVALID, "duplicate query index (matches must come from one knnMatch)");
     }
-    const int nf = res->n_feat, nd = res->n_depth, nt = res->n_triangulated, n_new = nd + nt;
-    if (nf < 0 || nf > cap_feat || nd < 0 || nt < 0 || n_new > nf)
-        return set_error(c, VX_ERR_STATE, "keyframe creation: %d depth + %d triangulated landmarks for %d features", nd,
-                         nt, nf);
-    // the host mirrors, as vx_dmap_add_landmarks / add_observations / set_features / add_keyframe leave them
+    if ((rc = check_counts(c, *res, cap_feat))) return rc;
+    const int n_new = res->n_depth + res->n_triangulated;
     K.rec.resize(n_new);
     if (n_new) std::memcpy(K.rec.data(), H + kRecOff, (size_t)n_new * sizeof(vx_keyframe_landmark));
-    m->lm_obs_live.resize(m->n_lm + n_new, 0);
-    m->lm_removed.resize(m->n_lm + n_new, 0);
-    m->feat_flags.resize((size_t)f0 + nf, 0);
-    int64_t oid = m->n_ids;
-    for (const vx_keyframe_landmark& r : K.rec) {
-        m->lm_index[r.lm_id] = r.row;
-        if (r.kind == 1) {
-            m->obs_index.emplace(std::make_pair((int)r.row, last_kf_id), oid++);
-            const int64_t g = f0_last + r.feat_last;
-            m->kf_valid_cnt[k_last] += 1 - (m->feat_flags[g] & 1);
-            m->feat_flags[g] = 1;
-        }
-        m->obs_index.emplace(std::make_pair((int)r.row, kf_id), oid++);
-        m->lm_obs_live[r.row] = r.kind == 1 ? 2 : 1;
-        m->feat_flags[f0 + r.feat_curr] = 1;
-    }
-    const int64_t n_obs_new = (int64_t)nd + 2 * (int64_t)nt;
-    m->n_lm += n_new;
-    m->n_lm_live += n_new;
-    m->n_obs += n_obs_new;
-    m->n_ids += n_obs_new;
-    m->n_obs_live += n_obs_new;
-    if (n_new) m->csr_dirty = true;
-    m->kf_index[kf_id] = (int)k;
-    m->kf_id.push_back(kf_id);
-    m->kf_feat_ptr.push_back(f0 + nf);
-    m->kf_has_cam.push_back(1);
-    m->kf_alive.push_back(1);
-    ++m->n_kf_live;
-    m->kf_valid_cnt.push_back(n_new);
+    commit_mirrors(m, K.rec.data(), *res, kf_id, last_kf_id, k_last);
     return VX_OK;
 }
 
 int check_common(vx_ctx* c, const vx_dmap* m, const double* pose7, const vx_keyframe_options* opt,
                  const vx_keyframe_result* res, const char* who) {
-    if (!m || !m->c || !pose7 || !opt || !res) return set_error(c, VX_ERR_INVALID, "%s: null argument", who);
-    if (m->c->device != c->device) return set_error(c, VX_ERR_INVALID, "map and context on different devices");
-    if (!(opt->tri_min_angle_deg == opt->tri_min_angle_deg) || !(opt->tri_max_reproj_error == opt->tri_max_reproj_error))
-        return set_error(c, VX_ERR_INVALID, "%s: NaN option", who);
-    return VX_OK;
+    if (!pose7 || !res) return set_error(c, VX_ERR_INVALID, "%s: null argument", who);
+    return kf::check_common(c, m, opt, who);
 }
 
 }  // namespace

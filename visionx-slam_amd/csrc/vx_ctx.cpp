@@ -176,7 +176,8 @@ static const char* kStageNames[vx::kStCount] = {
     "track_epairs",   "track_epose",   "init_sums",       "init_gate",
     "frame_capture",  "track_gate",    "track_final",
     "rig_pairs",      "rig_pack",      "rig_gate",        "rig_epairs",  "rig_epose",
-    "rig_final",      "frame_capture_batch"};
+    "rig_final",      "frame_capture_batch",
+    "rig_kf_feat",    "rig_kf_match",  "rig_kf_count",    "rig_kf_commit"};
 
 extern "C" {
 

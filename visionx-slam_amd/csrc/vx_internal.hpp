@@ -84,6 +84,10 @@ enum Stage : int {
     kStRigEPose,      // T_cl * T_lw per camera (k_rig_epose)
     kStRigFinal,      // the cameras' heads and packed blocks (k_rig_final)
     kStFrameCaptureBatch,  // a batch bank's frames into resident frames (k_frame_capture_batch)
+    kStRigKfFeat,     // CreateKeyFrame for a rig: feature rows + depth, camera = grid row (k_rig_kf_feat)
+    kStRigKfMatch,    // its triangulation gate per match (k_rig_kf_match)
+    kStRigKfCount,    // the cameras' landmark counts (k_rig_kf_count)
+    kStRigKfCommit,   // the cameras' ordered compactions and the map edit (k_rig_kf_commit)
     kStCount
 };
 

@@ -16,6 +16,7 @@
 #pragma once
 
 #include <memory>
+#include <utility>
 #include <vector>
 
 #include "visionx/feature.h"
@@ -53,11 +54,22 @@ public:
     // called; the depth image is uploaded, one copy per keyframe; the records and the host mirrors
     // are handled exactly as in the host-input form.  nullptr (default): the host-input form.
     void UseTrackLists(const FrameTracker* tracker) { tracks_ = tracker; }
+    // CreateKeyFrame for every (last, curr) pair of a rig time step, in order.  With a tracker attached
+    // (UseTrackLists), 1 .. VX_MAX_RIG_CAMERAS pairs, resident frames and the tracker's list for every
+    // pair that has a last frame — the state right after FrameTracker::TrackRig — it is ONE
+    // vx_dmap_create_keyframes_rig call (one upload, one synchronisation) followed by the reference's
+    // loop bodies, Map::InsertKeyFrame and DeviceMap::Created per camera over that camera's slice of the
+    // records.  In any other case it runs CreateKeyFrame pair by pair, which gives the same map, links
+    // and ids.  The cameras' last frames must be distinct keyframes of the map (the rig call refuses a
+    // shared one).  LastRecords() then holds all cameras' records.  Returns the next landmark_id_.
+    uint64_t CreateKeyFrameRig(const std::vector<std::pair<Frame::Ptr, Frame::Ptr>>& last_curr);
     const std::vector<vx_keyframe_landmark>& LastRecords() const { return rec_; }
 
     uint64_t landmark_id_ = 0;  // Tracking::landmark_id_ (tracking.h): next landmark id
 
 private:
+    void ApplyRecords(const Frame::Ptr& last_frame, const Frame::Ptr& curr_frame, const vx_keyframe_landmark* rec,
+                      size_t n);
     Map::Ptr map_;
     FeatureMatcher::Ptr matcher_;
     Options options_;

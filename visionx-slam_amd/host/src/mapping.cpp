@@ -175,9 +175,19 @@ uint64_t KeyFrameLandmarks::CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr cur
     int n_rec = 0;
     rec_.resize((size_t)res.n_depth + (size_t)res.n_triangulated);
     check(c, vx_dmap_create_results(dmap_->handle(), (int)rec_.size(), rec_.data(), &n_rec), "vx_dmap_create_results");
+    ApplyRecords(last_frame, curr_frame, rec_.data(), rec_.size());
+    landmark_id_ = res.next_landmark_id;
+    return landmark_id_;
+}
+
+// the loop bodies of tracking.cpp:634-643 and :915-925 over one keyframe's records, then :581
+void KeyFrameLandmarks::ApplyRecords(const Frame::Ptr& last_frame, const Frame::Ptr& curr_frame,
+                                     const vx_keyframe_landmark* rec, size_t n) {
+    auto& f2 = curr_frame->Features();
     std::vector<Landmark::Ptr> made;
-    made.reserve(rec_.size());
-    for (const vx_keyframe_landmark& r : rec_) {  // the loop bodies of tracking.cpp:634-643 and :915-925
+    made.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        const vx_keyframe_landmark& r = rec[i];
         auto lm = std::make_shared<Landmark>(r.lm_id, Vec3d(r.pw[0], r.pw[1], r.pw[2]));
         if (r.kind == 1) {
             lm->AddObservation(last_frame->Id(), (size_t)r.feat_last);
@@ -195,8 +205,71 @@ uint64_t KeyFrameLandmarks::CreateKeyFrame(Frame::Ptr last_frame, Frame::Ptr cur
         made.push_back(std::move(lm));
     }
     map_->InsertKeyFrame(curr_frame);  // tracking.cpp:581
-    dmap_->Created(rec_.empty() ? 0 : rec_.front().row, made, curr_frame);
-    landmark_id_ = res.next_landmark_id;
+    dmap_->Created(n ? rec[0].row : 0, made, curr_frame);
+}
+
+// tracking.cpp:577-581 for every camera of a rig step that inserts a keyframe
+uint64_t KeyFrameLandmarks::CreateKeyFrameRig(const std::vector<std::pair<Frame::Ptr, Frame::Ptr>>& last_curr) {
+    if (!dmap_) throw std::runtime_error("KeyFrameLandmarks::CreateKeyFrameRig: no DeviceMap (UseDeviceMap)");
+    // one rig call needs the map, 1 .. VX_MAX_RIG_CAMERAS resident current frames with a camera, and the
+    // tracker's own list for every pair that has a last frame; anything else goes pair by pair
+    const size_t n = last_curr.size();
+    bool rig = tracks_ && map_ && n >= 1 && n <= (size_t)VX_MAX_RIG_CAMERAS;
+    std::vector<vx_rig_keyframe> table(rig ? n : 0);
+    std::vector<double> host(rig ? 11 * n : 0);  // per camera: pose7 | intr4
+    for (size_t i = 0; rig && i < n; ++i) {
+        const Frame::Ptr& last = last_curr[i].first;
+        const Frame::Ptr& curr = last_curr[i].second;
+        if (!curr || !curr->Resident() || !curr->GetCamera() || (last && !last->Resident())) {
+            rig = false;
+            break;
+        }
+        vx_rig_keyframe& t = table[i];
+        t = vx_rig_keyframe{};
+        if (last && !tracks_->MatchList(last->Id(), curr->Id(), &t.d_matches, &t.d_n_matches, &t.cap_matches)) {
+            rig = false;
+            break;
+        }
+        const auto cam = curr->GetCamera();
+        double* T = &host[11 * i];
+        double* intr = T + 7;
+        pose7(curr->Pose(), T);
+        intr[0] = cam->fx(); intr[1] = cam->fy(); intr[2] = cam->cx(); intr[3] = cam->cy();
+        const DepthImage& depth = curr->Depth();
+        t.kf_id = curr->Id();
+        t.pose7 = T;
+        t.intr4 = intr;
+        t.curr = curr->Resident()->handle();
+        t.has_last = last ? 1 : 0;
+        t.last_kf_id = last ? last->Id() : 0;
+        t.depth = depth.empty() ? nullptr : depth.ptr();
+        t.depth_type = depth.type;
+        t.rows = depth.rows;
+        t.cols = depth.cols;
+        t.row_stride = (int64_t)depth.step;
+    }
+    if (!rig) {
+        for (const auto& p : last_curr) CreateKeyFrame(p.first, p.second);
+        return landmark_id_;
+    }
+    const vx_keyframe_options o{options_.triangulation_min_angle_deg, options_.triangulation_max_reproj_error};
+    dmap_->Flush();  // queued edits first: the call reads the resident map
+    vx_ctx* c = dmap_->context();
+    std::vector<vx_keyframe_result> res(n);
+    check(c, vx_dmap_create_keyframes_rig(c, dmap_->handle(), (int)n, table.data(), landmark_id_, &o, res.data()),
+          "vx_dmap_create_keyframes_rig");
+    size_t total = 0;
+    for (const vx_keyframe_result& r : res) total += (size_t)r.n_depth + (size_t)r.n_triangulated;
+    int n_rec = 0;
+    rec_.resize(total);
+    check(c, vx_dmap_create_results(dmap_->handle(), (int)rec_.size(), rec_.data(), &n_rec), "vx_dmap_create_results");
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {  // camera i's slice of the records, in camera order
+        const size_t k = (size_t)res[i].n_depth + (size_t)res[i].n_triangulated;
+        ApplyRecords(last_curr[i].first, last_curr[i].second, rec_.data() + at, k);
+        at += k;
+    }
+    landmark_id_ = res[n - 1].next_landmark_id;
     return landmark_id_;
 }
 

@@ -110,6 +110,7 @@ EXPORTS = [
     "vx_dmap_create_keyframe_frame",
     "vx_frame_capture_batch_async", "vx_track_rig_async", "vx_track_rig_fetch", "vx_track_rig_pairs",
     "vx_track_rig_keypoints", "vx_track_rig_matches", "vx_track_rig_layout", "vx_track_rig_block",
+    "vx_dmap_create_keyframes_rig",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -268,6 +269,8 @@ def lib():
         L.vx_dmap_create_results.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.vx_dmap_keyframe_features.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int)]
+        L.vx_dmap_create_keyframes_rig.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                   C.c_void_p]
         L.vx_ba_shard_of.restype = C.c_uint32
         L.vx_ba_shard_of.argtypes = [C.c_uint64, C.c_int]
         _lib = L
@@ -473,6 +476,14 @@ KEYFRAME_RESULT_DTYPE = np.dtype([("n_feat", "<i4"), ("n_depth", "<i4"), ("n_tri
 KEYFRAME_LANDMARK_DTYPE = np.dtype([("lm_id", "<u8"), ("row", "<i4"), ("kind", "<i4"), ("feat_curr", "<i4"),
                                     ("feat_last", "<i4"), ("pw", "<f8", 3)])
 KF_ERR_MATCH_RANGE, KF_ERR_DUP_QUERY, KF_ERR_KF_LIVE, KF_ERR_NO_LAST, KF_ERR_NO_CAMERA, KF_ERR_ID_RANGE = 1, 2, 4, 8, 16, 32
+KF_ERR_RIG_REPEAT = 64
+# vx_rig_keyframe (include/vx_slam.h; size pinned in csrc/keyframe_rig.hip): one camera of DMap.create_keyframes_rig
+RIG_KEYFRAME_DTYPE = np.dtype({"names": ["kf_id", "pose7", "intr4", "curr", "has_last", "last_kf_id", "d_matches",
+                                         "d_n_matches", "cap_matches", "depth", "depth_type", "rows", "cols",
+                                         "row_stride"],
+                               "formats": ["<u8", "<u8", "<u8", "<u8", "<i4", "<u8", "<u8", "<u8", "<i4", "<u8", "<i4",
+                                           "<i4", "<i4", "<i8"],
+                               "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 84, 88, 96], "itemsize": 104})
 
 
 def keyframe_options(**fields):
@@ -1676,6 +1687,42 @@ class DMap:
                                                  C.c_int(int(dt)), C.c_int(int(rows)), C.c_int(int(cols)),
                                                  C.c_int64(int(dstride)), C.c_uint64(int(first_landmark_id)), _p(o), _p(res))
         return self._create_done(c, rc, res)
+
+    def create_keyframes_rig(self, cams, first_landmark_id=0, opts=None, ctx=None):
+        """vx_dmap_create_keyframes_rig: Tracking::CreateKeyFrame for every camera of a rig step that
+        inserts a keyframe, in one call and one synchronisation.  cams: a list of dicts with
+        create_keyframe_frame's per-camera arguments ("kf_id", "pose7", "intr4", "frame", and optionally
+        "last_kf_id", "matches" (a device triple, Context.track_rig_matches(i, 0)), "depth" (a host 2-D
+        image)).  Returns {"results": KEYFRAME_RESULT_DTYPE[n], "landmarks": all cameras' records in
+        camera order}; camera i's slice follows from the results' counts.  A rejected call raises
+        VxError and commits nothing; the per-camera records (error_bits) are self.last_create_rig."""
+        c = self.ctx if ctx is None else ctx
+        tab = np.zeros(max(len(cams), 1), RIG_KEYFRAME_DTYPE)
+        keep = []  # the host arrays the table points to, alive until the call returns
+        for r, k in zip(tab, cams):
+            pose = np.ascontiguousarray(k["pose7"], np.float64)
+            assert pose.size == 7
+            intr = None if k.get("intr4") is None else np.ascontiguousarray(k["intr4"], np.float64)
+            assert intr is None or intr.size == 4
+            depth = None if k.get("depth") is None else np.ascontiguousarray(k["depth"])
+            keep += [pose, intr, depth]
+            m_ptr, mn_ptr, m_cap = k["matches"] if k.get("matches") is not None else (0, 0, 0)
+            last = k.get("last_kf_id")
+            r["kf_id"], r["pose7"], r["intr4"] = int(k["kf_id"]), pose.ctypes.data, 0 if intr is None else intr.ctypes.data
+            r["curr"] = int(k["frame"].handle.value or 0)
+            r["has_last"], r["last_kf_id"] = (0, 0) if last is None else (1, int(last))
+            r["d_matches"], r["d_n_matches"], r["cap_matches"] = int(m_ptr or 0), int(mn_ptr or 0), int(m_cap)
+            if depth is not None:
+                r["depth"], r["depth_type"] = depth.ctypes.data, DEPTH_TYPES[depth.dtype]
+                r["rows"], r["cols"], r["row_stride"] = depth.shape[0], depth.shape[1], depth.strides[0]
+        o = np.ascontiguousarray(keyframe_options() if opts is None else opts, KEYFRAME_OPTIONS_DTYPE)
+        res = np.zeros(max(len(cams), 1), KEYFRAME_RESULT_DTYPE)
+        rc = lib().vx_dmap_create_keyframes_rig(c.handle, self._h, len(cams), _p(tab), C.c_uint64(int(first_landmark_id)),
+                                                _p(o), _p(res))
+        del keep
+        self.last_create_rig = res[:len(cams)].copy()
+        c._check(rc)
+        return {"results": res[:len(cams)], "landmarks": self.create_results()}
 
     def create_results(self):
         """vx_dmap_create_results: the last create_keyframe*'s KEYFRAME_LANDMARK_DTYPE records."""
