@@ -90,6 +90,14 @@ def test_the_rules_are_stated_once():
                  "m->kf_valid_cnt.push_back(n_new)", "h.next_landmark_id = b.first_id() +"):
         hits = [f for f in os.listdir(csrc) if rule in rd(f)]
         assert len(hits) == 1, (rule, hits)
+    # ... and the host side fills their argument record and sizes a depth image by one statement each
+    for rule in ("a.first_id = ", "a.has_depth = ", "a.nf_last = ", "a.n_obs0 = ",                # KfArgs' filler
+                 "(size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(type)",            # depth_bytes
+                 "row_stride < (int64_t)cols * depth_elem(depth_type)"):                         # check_depth
+        hits = [f for f in os.listdir(csrc) if rule in rd(f)]
+        assert hits == ["keyframe_bodies.hpp"], (rule, hits)
+    hits = [f for f in os.listdir(csrc) if "size_t align64(" in rd(f)]
+    assert hits == ["vx_internal.hpp"], hits
 
 
 def rig_scene(sizes, depth, last, seed=64):

@@ -87,6 +87,23 @@ def test_layout_of_one_camera_is_the_single_calls():
     assert part(320, 320, 323)[:5] == (560, 560 + 1280, 560 + 1280 + 320, 560 + 1280 + 320 + 1280, 560 + 2 * (1280 + 320))
 
 
+EDGE = (0, 1, 15, 16, 17)  # where a 16-byte rounding term can go wrong
+
+
+def test_block_layout_against_the_second_statement():
+    """the library's Python statement of a block (vxslam.track_frame_block), this file's (part) and the C
+    one (vx_track_rig_layout: the end of a block is where a second camera's begins) agree"""
+    cases = [(a, b, k) for cp0, cp1, ckp in CAPS for a, b, k in zip(cp0, cp1, ckp)]
+    cases += [(a, b, k) for a in EDGE for b in EDGE for k in EDGE]
+    for cp0, cp1, ckp in cases:
+        want = part(cp0, cp1, ckp)
+        assert vxslam.track_frame_block(cp0, cp1, ckp) == want, (cp0, cp1, ckp)
+        off, total = vxslam.track_rig_layout([cp0, 3], [cp1, 5], [ckp, 7])
+        assert off[1] == want[-1] and total == want[-1] + part(3, 5, 7)[-1], (cp0, cp1, ckp)
+        # without the keypoint rows a block ends where they would begin
+        assert vxslam.track_rig_layout([cp0], [cp1], [0])[1] == want[4], (cp0, cp1, ckp)
+
+
 def test_layout_accepts_zero_capacities():
     off, total = vxslam.track_rig_layout([0, 0], [0, 0], [0, 0])
     head = a16(vxslam.TRACK_FRAME_RESULT_DTYPE.itemsize)
@@ -136,3 +153,23 @@ def test_the_rules_are_stated_once():
     for rule in ("a.offsets[1] = run ? n_pairs : 0", "a.offsets[1] = enough ? n_pairs : 0", "const bool open = !a.pnp"):
         hits = [f for f in os.listdir(csrc) if rule in rd(f)]
         assert len(hits) == 1, (rule, hits)
+    # ... and the host side fills and checks their argument records by one statement each
+    # (the map side of TrackArgs: other calls' records have an id table of their own, so among the tracking files)
+    hits = [f for f in os.listdir(csrc) if f.startswith("track") and "a.ht_mask = " in rd(f)]
+    assert hits == ["track_bodies.hpp"], hits
+    for rule in ("return mask(1) + align16((size_t)cap1);",            # the frame block's chain (o_mask1's term)
+                 "f.o_mask1 = ",                                       # FinalArgs' offsets
+                 "o.max_iterations < 0 ? 100 : o.max_iterations",      # PnP's hypothesis bound
+                 "a.opt_out = reinterpret_cast<OptOf<A>*>(prob + kProb1Opt);",  # the single problem record
+                 "constexpr size_t kProbOffsets = 0, kProbCnt = 128",  # the batch problem record
+                 "g.cap_last = ", "p.pose_last[i] = ", "a.mask = block + off_mask<R>(cap);",
+                 "intr4[0] + intr4[1] != 0.0", "bad PnP options", "bad essential options",
+                 "neither a last keyframe nor a last frame", "a last keyframe without a map / options",
+                 "const int np = which ? r->ess.n_pairs : r->pnp.n_pairs;"):
+        hits = [f for f in os.listdir(csrc) if rule in rd(f)]
+        assert hits == ["track_bodies.hpp"], (rule, hits)
+    # the staged upload (hipEventCreateWithFlags( of a plain hipEventDisableTiming event; vx_ctx.cpp's are the
+    # cross-stream ordering events): the helper, and frame.hip's own (it copies into a block it does not own)
+    ev = re.compile(r"hipEventCreateWithFlags\(&[^,]+, hipEventDisableTiming\)")
+    hits = sorted(f for f in os.listdir(csrc) if ev.search(rd(f)))
+    assert hits == ["frame.hip", "vx_internal.hpp"], hits

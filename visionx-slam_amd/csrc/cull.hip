@@ -470,8 +470,6 @@ __global__ void __launch_bounds__(kKfBlock) k_cull_rmkf(RmKfArgs a) {
     if (tid == 0) a.hdr[2] = n_out;
 }
 
-size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 struct Prep {
     std::vector<int> rows;  // live keyframe rows, ascending id
     KfTable kt{};

@@ -100,13 +100,8 @@ struct vx_dmap {
         vx::DevBuf dvalid, dpw, tvalid, tpw;  // depth per feature / triangulation per match
         vx::DevBuf aux;                       // winner per feature | qseen per last-keyframe feature | error word
         vx::PinnedBuf host;
-        vx::PinnedBuf in_host;                // vx_dmap_create_keyframe_host: one staged block ...
-        vx::DevBuf in;                        // ... uploaded in one copy
-        hipEvent_t in_event = nullptr;        // (recorded after that upload: the staging is reused once it has passed)
+        vx::StagedUpload in;                  // vx_dmap_create_keyframe_host: one staged block, uploaded in one copy
         std::vector<vx_keyframe_landmark> rec;
-        ~Create() {
-            if (in_event) (void)hipEventDestroy(in_event);
-        }
     } create;
     ~vx_dmap();
 };

@@ -314,11 +314,8 @@ int vx_init_gate_host_async(vx_ctx* c, const uint8_t* img, int width, int height
     const size_t row_bytes = (size_t)width * channels;
     const size_t o_xy = 16, o_img = o_xy + align16((size_t)n_feat * 8), bytes = o_img + row_bytes * height;
     // (the one place this entry can block: until the previous call's upload has left the staging)
-    if (c->ig_in_event) VX_HIP(c, hipEventSynchronize(c->ig_in_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&c->ig_in_event, hipEventDisableTiming));
-    VX_HIP(c, c->ig_in_host.ensure(bytes));
-    VX_HIP(c, c->ig_in.ensure(bytes));
-    uint8_t* h = static_cast<uint8_t*>(c->ig_in_host.p);
+    VX_HIP(c, c->ig_in.begin(bytes));
+    uint8_t* h = static_cast<uint8_t*>(c->ig_in.host.p);
     const int32_t counts[4] = {n_feat, 0, 0, 0};
     std::memcpy(h, counts, sizeof counts);
     if (xy_stride_bytes == 8) {
@@ -332,11 +329,10 @@ int vx_init_gate_host_async(vx_ctx* c, const uint8_t* img, int width, int height
     } else {
         for (int y = 0; y < height; ++y) std::memcpy(h + o_img + row_bytes * y, img + (int64_t)y * row_stride, row_bytes);
     }
-    VX_HIP(c, hipMemcpyAsync(c->ig_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(c->ig_in_event, c->stream));
-    const uint8_t* d = c->ig_in.as<uint8_t>();
+    VX_HIP(c, c->ig_in.upload(bytes, c->stream));
+    const uint8_t* d = c->ig_in.dev.as<uint8_t>();
     return vx_init_gate_async(c, d + o_img, width, height, channels, (int64_t)row_bytes,
-                              reinterpret_cast<const float*>(d + o_xy), 8, c->ig_in.as<int32_t>(), n_feat, opt);
+                              reinterpret_cast<const float*>(d + o_xy), 8, c->ig_in.dev.as<int32_t>(), n_feat, opt);
 }
 
 int vx_init_gate_fetch(vx_ctx* c, vx_init_gate_result* out) {

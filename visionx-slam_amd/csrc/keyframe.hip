@@ -41,7 +41,8 @@
 // launches (cap_feat landmarks, 2 cap_feat observations: a feature is linked at most once), so the
 // device sequence needs no count from the host.
 //
-// The kernels' program text lives in keyframe_bodies.hpp, shared with the rig form (keyframe_rig.hip).
+// The kernels' program text lives in keyframe_bodies.hpp, shared with the rig form (keyframe_rig.hip), as do the
+// record's filler (kf::fill_args over kf::Input) and the depth checks; the staging is m->create.in (vx::StagedUpload).
 #include "keyframe_bodies.hpp"
 
 namespace vx {
@@ -72,20 +73,6 @@ int reject(vx_ctx* c, vx_keyframe_result* res, int bits, const char* what) {
     return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe: %s", what);
 }
 
-struct Input {
-    const uint8_t* xy;
-    int64_t stride;
-    int xy_f64;
-    const int32_t* n_feat;
-    int cap_feat;
-    const vx_match* matches;
-    const int32_t* n_matches;
-    int cap_matches;
-    const void* depth;
-    int depth_type, rows, cols;
-    int64_t row_stride;
-};
-
 // the sequence over inputs already on the device, its one synchronisation, then the host mirrors
 int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const double* intr4, const Input& in,
                int has_last, uint64_t last_kf_id, uint64_t first_id, const vx_keyframe_options* opt,
@@ -110,13 +97,11 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     if (bits & VX_KF_ERR_NO_LAST) return reject(c, res, bits, "the last keyframe is not in the map");
     if (bits & VX_KF_ERR_NO_CAMERA) return reject(c, res, bits, "a keyframe without a camera");
     if (bits) return reject(c, res, bits, "a landmark id of the range is already in the map");
-    const bool has_depth = in.depth && in.rows > 0 && in.cols > 0;  // Depth().empty() (tracking.cpp:591-594)
     int rc;
-    if (has_depth && (rc = check_depth(c, in.depth_type, in.cols, in.row_stride))) return rc;
+    if (in.has_depth() && (rc = check_depth(c, in.depth_type, in.cols, in.row_stride))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
-    const int64_t k = (int64_t)m->kf_id.size(), f0 = m->kf_feat_ptr.back();
-    const int64_t f0_last = has_last ? m->kf_feat_ptr[k_last] : 0;
-    const int nf_last = has_last ? (int)(m->kf_feat_ptr[k_last + 1] - f0_last) : 0;
+    const int64_t f0 = m->kf_feat_ptr.back();
+    const int nf_last = has_last ? (int)(m->kf_feat_ptr[k_last + 1] - m->kf_feat_ptr[k_last]) : 0;
     if (m->n_lm + cap_feat > (int64_t)INT_MAX || f0 + cap_feat > (int64_t)INT_MAX)
         return set_error(c, VX_ERR_CAPACITY, "the map's rows would pass 2^31");
     const size_t cf = (size_t)cap_feat;
@@ -130,34 +115,8 @@ int create_run(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const double* pose7, const
     if (m->c != c && (rc = vx_stream_wait_ctx(c, m->c))) return rc;
 
     KfArgs a{};
-    a.kf_id = kf_id;
-    a.last_kf_id = last_kf_id;
-    a.xy = in.xy;
-    a.stride = in.stride;
-    a.xy_f64 = in.xy_f64;
-    a.n_feat = in.n_feat;
-    a.cap_feat = cap_feat;
-    a.has_depth = has_depth ? 1 : 0;
-    a.dv.depth = static_cast<const uint8_t*>(in.depth);
-    a.dv.type = in.depth_type;
-    a.dv.rows = in.rows;
-    a.dv.cols = in.cols;
-    a.dv.stride = in.row_stride;
-    camera_args(a, pose7, intr4, opt);
-    a.has_last = has_last ? 1 : 0;
-    a.k_last = k_last;
-    a.nf_last = nf_last;
-    a.f0_last = f0_last;
-    a.m = in.matches;
-    a.n_matches = in.n_matches;
-    a.cap_matches = cap_m;
-    map_pointers(a, m);
-    a.k_new = (int)k;
-    a.f0 = f0;
-    a.n_lm0 = m->n_lm;
-    a.n_obs0 = m->n_obs;
-    a.n_ids0 = m->n_ids;
-    a.first_id = first_id;
+    fill_args(a, m, in, kf_id, pose7, intr4, has_last != 0, last_kf_id, k_last, first_id, opt);
+    a.k_new = (int)m->kf_id.size();
     a.dvalid = K.dvalid.as<int>();
     a.dpw = K.dpw.as<double>();
     a.tvalid = K.tvalid.as<int>();
@@ -265,40 +224,31 @@ int vx_dmap_create_keyframe_host(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const do
     if (n_feat < 0 || (n_feat > 0 && !feat_uv) || n_matches < 0 || (has_last && n_matches > 0 && !matches))
         return set_error(c, VX_ERR_INVALID, "vx_dmap_create_keyframe_host: bad feature / match arguments");
     const bool has_depth = depth && rows > 0 && cols > 0;
-    if (has_depth) {
-        if (depth_type < VX_DEPTH_U16 || depth_type > VX_DEPTH_F64)
-            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", depth_type);
-        if (row_stride < (int64_t)cols * depth_elem(depth_type))
-            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
-    }
+    if (has_depth && (rc = check_depth(c, depth_type, cols, row_stride))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     auto& K = m->create;
     // one staged block: {n_feat, n_matches} | positions | matches | depth image
     const int nm = has_last ? n_matches : 0;
     const size_t o_uv = 64, o_m = align64(o_uv + (size_t)n_feat * 16), o_d = align64(o_m + (size_t)nm * sizeof(vx_match)),
-                 d_bytes = has_depth ? (size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(depth_type) : 0, bytes = align64(o_d + d_bytes);
+                 d_bytes = has_depth ? depth_bytes(depth_type, rows, cols, row_stride) : 0, bytes = align64(o_d + d_bytes);
     // (the one place this entry can block: until the previous call's upload has left the staging)
-    if (K.in_event) VX_HIP(c, hipEventSynchronize(K.in_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&K.in_event, hipEventDisableTiming));
-    VX_HIP(c, K.in_host.ensure(bytes));
-    VX_HIP(c, K.in.ensure(bytes));
-    uint8_t* h = static_cast<uint8_t*>(K.in_host.p);
+    VX_HIP(c, K.in.begin(bytes));
+    uint8_t* h = static_cast<uint8_t*>(K.in.host.p);
     const int32_t counts[4] = {n_feat, nm, 0, 0};
     std::memcpy(h, counts, sizeof counts);
     if (n_feat) std::memcpy(h + o_uv, feat_uv, (size_t)n_feat * 16);
     if (nm) std::memcpy(h + o_m, matches, (size_t)nm * sizeof(vx_match));
     if (d_bytes) std::memcpy(h + o_d, depth, d_bytes);
-    VX_HIP(c, hipMemcpyAsync(K.in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(K.in_event, c->stream));
-    const uint8_t* d = K.in.as<uint8_t>();
+    VX_HIP(c, K.in.upload(bytes, c->stream));
+    const uint8_t* d = K.in.dev.as<uint8_t>();
     Input in{};
     in.xy = d + o_uv;
     in.stride = 16;
     in.xy_f64 = 1;
-    in.n_feat = K.in.as<int32_t>();
+    in.n_feat = K.in.dev.as<int32_t>();
     in.cap_feat = n_feat;
     in.matches = reinterpret_cast<const vx_match*>(d + o_m);
-    in.n_matches = K.in.as<int32_t>() + 1;
+    in.n_matches = K.in.dev.as<int32_t>() + 1;
     in.cap_matches = nm;
     in.depth = has_depth ? d + o_d : nullptr;
     in.depth_type = depth_type;
@@ -321,23 +271,16 @@ int vx_dmap_create_keyframe_frame(vx_ctx* c, vx_dmap* m, uint64_t kf_id, const d
     const bool has_depth = depth && rows > 0 && cols > 0;
     const void* d_depth = nullptr;
     if (has_depth) {
-        if (depth_type < VX_DEPTH_U16 || depth_type > VX_DEPTH_F64)
-            return set_error(c, VX_ERR_INVALID, "unknown depth type %d", depth_type);
-        if (row_stride < (int64_t)cols * depth_elem(depth_type))
-            return set_error(c, VX_ERR_INVALID, "row_stride < cols * element size");
+        if ((rc = check_depth(c, depth_type, cols, row_stride))) return rc;
         VX_HIP(c, hipSetDevice(c->device));
         // the depth image is the one thing that still comes from the host: one copy per keyframe,
         // through the staging vx_dmap_create_keyframe_host uses (and its event)
         auto& K = m->create;
-        const size_t d_bytes = (size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(depth_type), bytes = align64(d_bytes);
-        if (K.in_event) VX_HIP(c, hipEventSynchronize(K.in_event));
-        else VX_HIP(c, hipEventCreateWithFlags(&K.in_event, hipEventDisableTiming));
-        VX_HIP(c, K.in_host.ensure(bytes));
-        VX_HIP(c, K.in.ensure(bytes));
-        std::memcpy(K.in_host.p, depth, d_bytes);
-        VX_HIP(c, hipMemcpyAsync(K.in.p, K.in_host.p, bytes, hipMemcpyHostToDevice, c->stream));
-        VX_HIP(c, hipEventRecord(K.in_event, c->stream));
-        d_depth = K.in.p;
+        const size_t d_bytes = depth_bytes(depth_type, rows, cols, row_stride), bytes = align64(d_bytes);
+        VX_HIP(c, K.in.begin(bytes));
+        std::memcpy(K.in.host.p, depth, d_bytes);
+        VX_HIP(c, K.in.upload(bytes, c->stream));
+        d_depth = K.in.dev.p;
     }
     return vx_dmap_create_keyframe(c, m, kf_id, pose7, intr4, &curr->kp()->x, (int64_t)sizeof(vx_keypoint), curr->count(),
                                    curr->cap, has_last, last_kf_id, d_matches, d_n_matches, cap_matches, d_depth, depth_type,

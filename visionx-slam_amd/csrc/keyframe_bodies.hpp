@@ -5,7 +5,7 @@
 // A body reads its arguments as (KfArgs, a base): everything a camera's call fixes on the host, and
 // the five places its new rows follow.  The single call's kernels pass the record's own counts (OwnBase); the
 // rig kernels pass the same record read from a table entry and a RigBase advanced by the counts of the
-// cameras before it.  The host side shares the array growth, the argument checks and the host
+// cameras before it.  The host side shares the array growth, the record's filler, the argument checks and the host
 // mirrors' update (commit_mirrors), which both forms run per camera in camera order.
 #pragma once
 #include <algorithm>
@@ -326,9 +326,62 @@ inline void camera_args(KfArgs& a, const double* pose7, const double* intr4, con
     for (int j = 0; j < 4; ++j) a.intr[j] = intr4[j];
 }
 
-inline size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+// one camera's inputs on the device: feature rows, match list, depth image
+struct Input {
+    const uint8_t* xy;
+    int64_t stride;
+    int xy_f64;
+    const int32_t* n_feat;
+    int cap_feat;
+    const vx_match* matches;
+    const int32_t* n_matches;
+    int cap_matches;
+    const void* depth;
+    int depth_type, rows, cols;
+    int64_t row_stride;
+    bool has_depth() const { return depth && rows > 0 && cols > 0; }  // Depth().empty() (tracking.cpp:591-594)
+};
+
+// Everything of a camera's record that the single call and the rig call set alike: ids, feature rows, depth
+// view, camera, the last keyframe (row k_last), the match list, the map's arrays (after grow_map) and the
+// CALL's bases.  The caller adds k_new, its scratch and its pinned outputs.
+inline void fill_args(KfArgs& a, const vx_dmap* m, const Input& in, uint64_t kf_id, const double* pose7, const double* intr4,
+                      bool has_last, uint64_t last_kf_id, int k_last, uint64_t first_id, const vx_keyframe_options* opt) {
+    a.kf_id = kf_id;
+    a.last_kf_id = last_kf_id;
+    a.first_id = first_id;
+    a.xy = in.xy;
+    a.stride = in.stride;
+    a.xy_f64 = in.xy_f64;
+    a.n_feat = in.n_feat;
+    a.cap_feat = in.cap_feat;
+    a.has_depth = in.has_depth() ? 1 : 0;
+    a.dv.depth = static_cast<const uint8_t*>(in.depth);
+    a.dv.type = in.depth_type;
+    a.dv.rows = in.rows;
+    a.dv.cols = in.cols;
+    a.dv.stride = in.row_stride;
+    camera_args(a, pose7, intr4, opt);
+    a.has_last = has_last ? 1 : 0;
+    a.k_last = k_last;
+    a.f0_last = has_last ? m->kf_feat_ptr[k_last] : 0;
+    a.nf_last = has_last ? (int)(m->kf_feat_ptr[k_last + 1] - a.f0_last) : 0;
+    a.m = in.matches;
+    a.n_matches = in.n_matches;
+    a.cap_matches = has_last ? in.cap_matches : 0;
+    map_pointers(a, m);
+    a.f0 = m->kf_feat_ptr.back();
+    a.n_lm0 = m->n_lm;
+    a.n_obs0 = m->n_obs;
+    a.n_ids0 = m->n_ids;
+}
 
 inline int depth_elem(int type) { return type == VX_DEPTH_U16 ? 2 : (type == VX_DEPTH_F32 ? 4 : 8); }
+
+// bytes of a rows x cols image whose last row carries no padding
+inline size_t depth_bytes(int type, int rows, int cols, int64_t row_stride) {
+    return (size_t)row_stride * (rows - 1) + (size_t)cols * depth_elem(type);
+}
 
 inline int check_depth(vx_ctx* c, int depth_type, int cols, int64_t row_stride) {
     if (depth_type < VX_DEPTH_U16 || depth_type > VX_DEPTH_F64)

@@ -39,9 +39,9 @@
 // lies beyond the map's used counts, so a rejected call leaves the map as it was.
 //
 // The per-camera argument records (KfArgs, keyframe_bodies.hpp) and the cameras' HOST depth images are
-// staged in one pinned block (the single call's staging, guarded by its event) and uploaded in one copy;
+// staged in one pinned block (the single call's staging, m->create.in, guarded by its event) and uploaded in one copy;
 // the kernels read their entry through uniform addresses.  The kernels run the single call's program
-// text (keyframe_bodies.hpp).  Resources (-Rpass-analysis=kernel-resource-usage, gfx950): DESIGN §34.
+// text and their records are filled by its filler, kf::fill_args (keyframe_bodies.hpp).  Resources (-Rpass-analysis=kernel-resource-usage, gfx950): DESIGN §34.
 #include "keyframe_bodies.hpp"
 
 namespace vx {
@@ -156,7 +156,7 @@ int vx_dmap_create_keyframes_rig(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig
         d_bytes[i] = 0;
         if (has_depth[i]) {
             if ((rc = check_depth(c, k.depth_type, k.cols, k.row_stride))) return rc;
-            d_bytes[i] = (size_t)k.row_stride * (k.rows - 1) + (size_t)k.cols * depth_elem(k.depth_type);
+            d_bytes[i] = depth_bytes(k.depth_type, k.rows, k.cols, k.row_stride);
         }
         sum_feat += k.curr->cap;
         sum_m += k.has_last ? k.cap_matches : 0;
@@ -224,12 +224,9 @@ int vx_dmap_create_keyframes_rig(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig
         bytes += align64(d_bytes[i]);
     }
     // (the one place this entry can block: until the previous call's upload has left the staging)
-    if (K.in_event) VX_HIP(c, hipEventSynchronize(K.in_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&K.in_event, hipEventDisableTiming));
-    VX_HIP(c, K.in_host.ensure(bytes));
-    VX_HIP(c, K.in.ensure(bytes));
-    uint8_t* h = static_cast<uint8_t*>(K.in_host.p);
-    const uint8_t* d = K.in.as<uint8_t>();
+    VX_HIP(c, K.in.begin(bytes));
+    uint8_t* h = static_cast<uint8_t*>(K.in.host.p);
+    const uint8_t* d = K.in.dev.as<uint8_t>();
     uint8_t* H = static_cast<uint8_t*>(K.host.p);
     int* winner = K.aux.as<int>();
     int* qseen = winner + cf;
@@ -238,36 +235,23 @@ int vx_dmap_create_keyframes_rig(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig
     KfArgs* tab = reinterpret_cast<KfArgs*>(h);
     for (int i = 0; i < n_cams; ++i) {
         const vx_rig_keyframe& k = cams[i];
+        Input in{};
+        in.xy = reinterpret_cast<const uint8_t*>(&k.curr->kp()->x);
+        in.stride = (int64_t)sizeof(vx_keypoint);
+        in.n_feat = k.curr->count();
+        in.cap_feat = k.curr->cap;
+        in.matches = k.d_matches;
+        in.n_matches = k.d_n_matches;
+        in.cap_matches = k.cap_matches;
+        in.depth = has_depth[i] ? d + o_depth[i] : nullptr;
+        in.depth_type = k.depth_type;
+        in.rows = has_depth[i] ? k.rows : 0;
+        in.cols = has_depth[i] ? k.cols : 0;
+        in.row_stride = k.row_stride;
         KfArgs a{};
-        a.kf_id = k.kf_id;
-        a.last_kf_id = k.last_kf_id;
-        a.xy = reinterpret_cast<const uint8_t*>(&k.curr->kp()->x);
-        a.stride = (int64_t)sizeof(vx_keypoint);
-        a.xy_f64 = 0;
-        a.n_feat = k.curr->count();
-        a.cap_feat = k.curr->cap;
-        a.has_depth = has_depth[i] ? 1 : 0;
-        a.dv.depth = has_depth[i] ? d + o_depth[i] : nullptr;
-        a.dv.type = k.depth_type;
-        a.dv.rows = has_depth[i] ? k.rows : 0;
-        a.dv.cols = has_depth[i] ? k.cols : 0;
-        a.dv.stride = k.row_stride;
-        camera_args(a, k.pose7, k.intr4, opt);
-        a.has_last = k.has_last ? 1 : 0;
-        a.k_last = k_last[i];
-        a.nf_last = nf_last[i];
-        a.f0_last = k.has_last ? m->kf_feat_ptr[k_last[i]] : 0;
-        a.m = k.d_matches;
-        a.n_matches = k.d_n_matches;
-        a.cap_matches = k.has_last ? k.cap_matches : 0;
-        map_pointers(a, m);
+        // (the bases it sets are the CALL's: the kernels advance them by the cameras before this one)
+        fill_args(a, m, in, k.kf_id, k.pose7, k.intr4, k.has_last != 0, k.last_kf_id, k_last[i], first_landmark_id, opt);
         a.k_new = (int)(k0 + i);
-        // the CALL's bases: the kernels advance them by the cameras before this one
-        a.f0 = f0;
-        a.n_lm0 = m->n_lm;
-        a.n_obs0 = m->n_obs;
-        a.n_ids0 = m->n_ids;
-        a.first_id = first_landmark_id;
         a.rec = reinterpret_cast<vx_keyframe_landmark*>(H + kRigRecOff);
         a.dvalid = K.dvalid.as<int>() + o_feat[i];
         a.dpw = K.dpw.as<double>() + 3 * o_feat[i];
@@ -280,9 +264,8 @@ int vx_dmap_create_keyframes_rig(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig
         std::memcpy(tab + i, &a, sizeof a);
         if (d_bytes[i]) std::memcpy(h + o_depth[i], k.depth, d_bytes[i]);
     }
-    VX_HIP(c, hipMemcpyAsync(K.in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(K.in_event, c->stream));
-    const KfArgs* dtab = K.in.as<KfArgs>();
+    VX_HIP(c, K.in.upload(bytes, c->stream));
+    const KfArgs* dtab = K.in.dev.as<KfArgs>();
 
     // ---- one memset (every camera's qseen slice and error word) and four launches
     VX_HIP(c, hipMemsetAsync(qseen, 0, (cl + (size_t)kP) * sizeof(int), c->stream));

@@ -40,6 +40,9 @@
 // (58 VGPRs, no scratch); LDS: 16 wave counts + 16 wave minima + 16 wave doubles = 256 B.
 // The hash probe and the lm_bad / lm_pos reads behind it are the only loads whose address depends
 // on another load of the same stage beyond the match record itself.
+//
+// Host side: TrackArgs is filled and the options checked by track_bodies.hpp's host section; the host-input form
+// stages its upload in c->tk_in (vx::StagedUpload, vx_internal.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -111,15 +114,13 @@ int vx_track_pnp_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const float* 
     const auto kf = m->kf_index.find(last_kf_id);
     if (kf == m->kf_index.end())
         return set_error(c, VX_ERR_INVALID, "keyframe %llu is not in the map", (unsigned long long)last_kf_id);
-    if (!(intr4[0] != 0.0 && intr4[1] != 0.0)) return set_error(c, VX_ERR_INVALID, "zero focal length");
-    if (opt->pnp.max_iterations > 4096)
-        return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", opt->pnp.max_iterations);
-    if (opt->pnp.refine_iterations < 0 || !(opt->pnp.reproj_error >= 0.0))
-        return set_error(c, VX_ERR_INVALID, "bad PnP options");
+    // (fx + fy != 0 is NOT tested here, unlike trk::check_focal: track_bodies.hpp)
+    if (!(intr4[0] != 0.0 && intr4[1] != 0.0)) return set_error(c, VX_ERR_INVALID, "vx_track_pnp_async: zero focal length");
+    int rc;
+    if ((rc = trk::check_pnp_options(c, "vx_track_pnp_async", opt->pnp))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     // the id table must hold the landmarks added since the last LocalBA; it belongs to the map, so it
     // is brought up to date on the map context's stream, which this context's stream then follows
-    int rc;
     if ((rc = ht_sync(m->c, m))) return set_error(c, rc, "landmark id table: %s", vx_last_error(m->c));
     if ((rc = vx_stream_wait_ctx(c, m->c))) return rc;
 
@@ -127,11 +128,8 @@ int vx_track_pnp_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const float* 
     VX_HIP(c, c->tk_good.ensure((size_t)cap * sizeof(int)));
     VX_HIP(c, c->tk_obj.ensure((size_t)cap * 3 * sizeof(float)));
     VX_HIP(c, c->tk_img.ensure((size_t)cap * 2 * sizeof(float)));
-    VX_HIP(c, c->tk_prob.ensure(16 + 4 * sizeof(double) + sizeof(vx_pnp_options)));
+    VX_HIP(c, c->tk_prob.ensure(trk::prob1_bytes<TrackArgs>()));
     VX_HIP(c, c->tk_out.ensure(packed_bytes(cap)));
-    uint8_t* prob = c->tk_prob.as<uint8_t>();
-    uint8_t* out = c->tk_out.as<uint8_t>();
-    const int k = kf->second;
     TrackArgs a{};
     a.matches = d_matches;
     a.n_matches = d_n_matches;
@@ -139,29 +137,13 @@ int vx_track_pnp_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const float* 
     a.curr_xy = reinterpret_cast<const uint8_t*>(d_curr_xy);
     a.stride = curr_stride_bytes;
     a.n_curr = d_n_curr;
-    a.f0 = m->kf_feat_ptr[k];
-    a.nf = (int)(m->kf_feat_ptr[k + 1] - m->kf_feat_ptr[k]);
-    a.feat_uv = m->feat_uv.as<double>();
-    a.feat_lm = m->feat_lm.as<uint64_t>();
-    a.feat_fl = m->feat_fl.as<uint8_t>();
-    a.ht_key = m->ht_key.as<uint64_t>();
-    a.ht_val = m->ht_val.as<int>();
-    a.ht_mask = m->ht_cap - 1;
-    a.lm_bad = m->lm_bad.as<uint8_t>();
-    a.lm_pos = m->lm_pos.as<double>();
-    a.min_matches = opt->min_matches;
-    a.min_inliers = opt->min_inliers;
-    a.pnp = opt->pnp;
-    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+    trk::map_side(a, m, kf->second);
+    trk::set_options(a, *opt, intr4);
     a.good = c->tk_good.as<int>();
     a.obj = c->tk_obj.as<float>();
     a.img = c->tk_img.as<float>();
-    a.pair_match = reinterpret_cast<int*>(out + off_pair_match());
-    a.mask = out + off_mask(cap);
-    a.res = reinterpret_cast<vx_track_result*>(out);
-    a.offsets = reinterpret_cast<int*>(prob);
-    a.intr_out = reinterpret_cast<double*>(prob + 16);
-    a.opt_out = reinterpret_cast<vx_pnp_options*>(prob + 16 + 4 * sizeof(double));
+    trk::packed_outputs(a, c->tk_out.as<uint8_t>(), cap);
+    trk::prob1_pointers(a, c->tk_prob.as<uint8_t>());
     c->tk_valid = false;
     VX_HIP(c, launch(c, kStTrackPairs, k_track_pairs, dim3(1), dim3(kBlock), 0, c->stream, a));
     PnpDeviceArgs d{};
@@ -172,9 +154,7 @@ int vx_track_pnp_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const float* 
     d.img = a.img;
     d.out = &a.res->pnp;
     d.mask = a.mask;
-    // the hypothesis grid is the host-side bound of the budget; k_pnp_hyp exits beyond the resolved one
-    const int hmax = std::max(1, opt->pnp.max_iterations < 0 ? 100 : opt->pnp.max_iterations);
-    if ((rc = pnp_enqueue(c, 1, hmax, d, c->tk_hyp))) return rc;
+    if ((rc = pnp_enqueue(c, 1, trk::pnp_hyp_bound(opt->pnp), d, c->tk_hyp))) return rc;
     c->tk_cap = cap;
     c->tk_min_matches = opt->min_matches;
     c->tk_min_inliers = opt->min_inliers;
@@ -196,11 +176,8 @@ int vx_track_pnp_host_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const ui
     const size_t o_q = 16, o_t = o_q + (size_t)cap_q * 32, o_xy = o_t + (size_t)cap_t * 32,
                  bytes = o_xy + (size_t)cap_t * 8;
     // (the one place this entry can block: until the previous call's upload has left the staging)
-    if (c->tk_in_event) VX_HIP(c, hipEventSynchronize(c->tk_in_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&c->tk_in_event, hipEventDisableTiming));
-    VX_HIP(c, c->tk_in_host.ensure(bytes));
-    VX_HIP(c, c->tk_in.ensure(bytes));
-    uint8_t* h = static_cast<uint8_t*>(c->tk_in_host.p);
+    VX_HIP(c, c->tk_in.begin(bytes));
+    uint8_t* h = static_cast<uint8_t*>(c->tk_in.host.p);
     const int32_t counts[4] = {n_query, n_train, 0, 0};
     std::memcpy(h, counts, sizeof counts);
     // rows between the counts and the rounded capacities are not filled: the match kernels stop at
@@ -210,10 +187,9 @@ int vx_track_pnp_host_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const ui
         std::memcpy(h + o_t, train_desc, (size_t)n_train * 32);
         std::memcpy(h + o_xy, curr_xy, (size_t)n_train * 8);
     }
-    VX_HIP(c, hipMemcpyAsync(c->tk_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(c->tk_in_event, c->stream));
-    const uint8_t* d = c->tk_in.as<uint8_t>();
-    const int32_t* dn = c->tk_in.as<int32_t>();
+    VX_HIP(c, c->tk_in.upload(bytes, c->stream));
+    const uint8_t* d = c->tk_in.dev.as<uint8_t>();
+    const int32_t* dn = c->tk_in.dev.as<int32_t>();
     int rc;
     if ((rc = vx_match_device_async(c, d + o_q, dn, cap_q, d + o_t, dn + 1, cap_t, ratio))) return rc;
     // the list just enqueued, named explicitly with the capacity it was enqueued with

@@ -8,9 +8,17 @@
 // functions over an argument record they cost the single-camera kernels 2 VGPRs and a 28 - 44 KB LDS
 // promotion of the record.  Either way the single-camera kernels compile to what they were
 // (-Rpass-analysis=kernel-resource-usage figures unchanged: DESIGN.md §32).
+// The host section at the end states once how the entry points fill and check these records;
+// it is here, not in a header of its own, so that a record and its filler are read and changed together, as
+// keyframe_bodies.hpp keeps map_pointers / camera_args / check_depth beside KfArgs.
 #pragma once
 
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+
 #include "vx_internal.hpp"
+#include "dmap.hpp"
 #include "lm_hash.hpp"
 #include "track_common.hpp"
 #include "vx_rows.hpp"
@@ -256,6 +264,173 @@ __device__ __forceinline__ void track_final(const FinalArgs a, const uint8_t* ma
     for (int k = 0; k < 7; ++k) out->pose[k] = pose[k];
     out->pnp_ran = pnp_ran;
     out->ess_ran = ess_ran;
+}
+
+// ---------------------------------------------------------------- host side
+// How the entry points (track.hip, track_ess.hip, track_frame.hip, track_rig.hip) fill the records
+// above and check what goes into them: ONE statement of each, beside the record it fills.
+
+// Track()'s packed block: vx_track_frame_result | pair_match0 | mask0 | pair_match1 | mask1 | keypoint
+// rows, each part on a 16-byte boundary.  The only place the chain is written.
+inline size_t FrameBlock::pm(int which) const {
+    return align16(sizeof(vx_track_frame_result)) + (which ? align16((size_t)cap0 * 4) + align16((size_t)cap0) : 0);
+}
+inline size_t FrameBlock::mask(int which) const { return pm(which) + align16((size_t)(which ? cap1 : cap0) * 4); }
+inline size_t FrameBlock::kp() const { return mask(1) + align16((size_t)cap1); }
+inline size_t FrameBlock::bytes(bool with_keypoints) const {
+    return kp() + (with_keypoints ? align16((size_t)cap_kp * sizeof(vx_keypoint)) : 0);
+}
+
+// a path's pair arrays out of a fetched block h (vx_track_frame_pairs, vx_track_rig_pairs)
+inline int copy_pairs(vx_ctx* c, const uint8_t* h, const FrameBlock& b, int which, int32_t* pair_match, uint8_t* mask,
+                      int cap_pairs) {
+    const vx_track_frame_result* r = reinterpret_cast<const vx_track_frame_result*>(h);
+    const int np = which ? r->ess.n_pairs : r->pnp.n_pairs;
+    if ((pair_match || mask) && np > cap_pairs) return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
+    if (pair_match && np) std::memcpy(pair_match, h + b.pm(which), (size_t)np * 4);
+    if (mask && np) std::memcpy(mask, h + b.mask(which), (size_t)np);
+    return VX_OK;
+}
+
+// the map side of TrackArgs: keyframe row k's feature rows, the landmark arrays and their id table
+inline void map_side(TrackArgs& a, const vx_dmap* m, int k) {
+    a.f0 = m->kf_feat_ptr[k];
+    a.nf = (int)(m->kf_feat_ptr[k + 1] - m->kf_feat_ptr[k]);
+    a.feat_uv = m->feat_uv.as<double>();
+    a.feat_lm = m->feat_lm.as<uint64_t>();
+    a.feat_fl = m->feat_fl.as<uint8_t>();
+    a.ht_key = m->ht_key.as<uint64_t>();
+    a.ht_val = m->ht_val.as<int>();
+    a.ht_mask = m->ht_cap - 1;
+    a.lm_bad = m->lm_bad.as<uint8_t>();
+    a.lm_pos = m->lm_pos.as<double>();
+}
+
+// options and intrinsics of the two pair records
+inline void set_options(TrackArgs& a, const vx_track_options& o, const double* intr4) {
+    a.min_matches = o.min_matches;
+    a.min_inliers = o.min_inliers;
+    a.pnp = o.pnp;
+    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+}
+inline void set_options(EPairArgs& a, const vx_track_essential_options& o, const double* intr4) {
+    a.min_matches = o.min_matches;
+    a.ess = o.ess;
+    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+}
+// PnP's hypothesis grid: the host-side bound of the budget (k_pnp_hyp exits beyond the resolved one)
+inline int pnp_hyp_bound(const vx_pnp_options& o) { return std::max(1, o.max_iterations < 0 ? 100 : o.max_iterations); }
+
+// A = TrackArgs or EPairArgs: its packed block R | pair_match[cap] | mask[cap] (track_common.hpp) at `block`
+template <class A>
+inline void packed_outputs(A& a, uint8_t* block, int cap) {
+    using R = typename std::remove_pointer<decltype(a.res)>::type;
+    a.pair_match = reinterpret_cast<int*>(block + off_pair_match<R>());
+    a.mask = block + off_mask<R>(cap);
+    a.res = reinterpret_cast<R*>(block);
+}
+
+// The problem record a pair kernel leaves for its RANSAC.  One problem: offsets[2] | intr[4] | options.
+// A batch: offsets[P + 1] | the cameras' {0, n} records | intr[4 P] | options[P].
+template <class A>
+using OptOf = typename std::remove_pointer<decltype(A::opt_out)>::type;
+constexpr size_t kProb1Intr = 16, kProb1Opt = kProb1Intr + 4 * sizeof(double);
+template <class A>
+constexpr size_t prob1_bytes() { return kProb1Opt + sizeof(OptOf<A>); }
+template <class A>
+inline void prob1_pointers(A& a, uint8_t* prob) {
+    a.offsets = reinterpret_cast<int*>(prob);
+    a.intr_out = reinterpret_cast<double*>(prob + kProb1Intr);
+    a.opt_out = reinterpret_cast<OptOf<A>*>(prob + kProb1Opt);
+}
+constexpr int kProbMax = VX_MAX_RIG_CAMERAS;
+constexpr size_t kProbOffsets = 0, kProbCnt = 128, kProbIntr = 256, kProbOpt = 768;
+static_assert((kProbMax + 1) * sizeof(int) <= 128 && 2 * kProbMax * sizeof(int) <= 128 && 4 * kProbMax * sizeof(double) <= 512,
+              "problem record");
+template <class A>
+constexpr size_t prob_bytes() { return kProbOpt + kProbMax * sizeof(OptOf<A>); }
+template <class A>
+inline void prob_pointers(A& a, uint8_t* prob, int i) {  // problem i of a batch
+    a.offsets = reinterpret_cast<int*>(prob + kProbCnt) + 2 * i;
+    a.intr_out = reinterpret_cast<double*>(prob + kProbIntr) + 4 * i;
+    a.opt_out = reinterpret_cast<OptOf<A>*>(prob + kProbOpt) + i;
+}
+
+// pnp: the PnP record the decision reads (NULL: no last keyframe; po is not read then); last: NULL without a
+// last frame.  n_matches0 / n_matches1 (list 1 sharing list 0's rows) stay with the caller.
+inline void gate_args(GateArgs& g, const vx_track_result* pnp, const vx_track_options* po, const vx_frame* last, int* gate) {
+    g.pnp = pnp;
+    g.min_matches = pnp ? po->min_matches : 0;
+    g.min_inliers = pnp ? po->min_inliers : 0;
+    g.n_last = last ? last->count() : nullptr;
+    g.cap_last = last ? last->cap : 0;
+    g.gate = gate;
+}
+
+inline void epose_args(EPoseArgs& p, vx_track_essential_result* res, const double* pose_last7) {
+    p.res = res;
+    for (int i = 0; i < 7; ++i) p.pose_last[i] = pose_last7 ? pose_last7[i] : (i == 3 ? 1.0 : 0.0);
+}
+
+// tk (NULL: no last keyframe) / te: the two paths' packed blocks, of b.cap0 / b.cap1 pairs
+inline void final_args(FinalArgs& f, const uint8_t* tk, const uint8_t* te, const FrameBlock& b, const int* gate,
+                       bool has_last, const vx_track_essential_options& eo, const vx_frame* curr, uint8_t* out) {
+    f.tk = tk;
+    f.tk_cap = b.cap0;
+    f.te = te;
+    f.te_cap = b.cap1;
+    f.gate = gate;
+    f.has_last = has_last ? 1 : 0;
+    f.ess_min_matches = eo.min_matches;
+    f.ess_min_inliers = eo.min_inliers;
+    f.kp = reinterpret_cast<const uint8_t*>(curr->kp());
+    f.n_kp = curr->count();
+    f.cap_kp = b.cap_kp;
+    f.out = out;
+    f.o_pm0 = b.pm(0);
+    f.o_mask0 = b.mask(0);
+    f.o_pm1 = b.pm(1);
+    f.o_mask1 = b.mask(1);
+    f.o_kp = b.kp();
+}
+
+// The checks, each under the text that names the call (and the camera).  NOTE the two focal-length
+// predicates differ: vx_track_pnp_async tests fx != 0 && fy != 0 only (track.hip), the essential path and
+// the rig also fx + fy != 0 (check_focal).  Left as they are: unifying them changes what is refused.
+inline int check_focal(vx_ctx* c, const char* who, const double* intr4) {
+    if (intr4[0] != 0.0 && intr4[1] != 0.0 && intr4[0] + intr4[1] != 0.0) return VX_OK;
+    return set_error(c, VX_ERR_INVALID, "%s: zero focal length", who);
+}
+inline int check_pnp_options(vx_ctx* c, const char* who, const vx_pnp_options& o) {
+    if (o.max_iterations > 4096) return set_error(c, VX_ERR_INVALID, "%s: max_iterations %d > 4096", who, o.max_iterations);
+    if (o.refine_iterations < 0 || !(o.reproj_error >= 0.0)) return set_error(c, VX_ERR_INVALID, "%s: bad PnP options", who);
+    return VX_OK;
+}
+inline int check_ess_options(vx_ctx* c, const char* who, const vx_essential_options& o) {
+    if (o.max_iterations > 4096) return set_error(c, VX_ERR_INVALID, "%s: max_iterations %d > 4096", who, o.max_iterations);
+    if (!(o.threshold >= 0.0)) return set_error(c, VX_ERR_INVALID, "%s: bad essential options", who);
+    return VX_OK;
+}
+// the host values of the essential path, before anything touches a device
+inline int check_ess_host_args(vx_ctx* c, const char* who, const double* intr4, const vx_track_essential_options* opt) {
+    if (!intr4 || !opt) return set_error(c, VX_ERR_INVALID, "%s: null intrinsics / options", who);
+    int rc;
+    if ((rc = check_focal(c, who, intr4))) return rc;
+    return check_ess_options(c, who, opt->ess);
+}
+// One camera's frames: a current frame and intrinsics, a last keyframe or a last frame, all on the context's
+// device, the last keyframe in the map.  map_ok: a last keyframe has the map and the options it needs.
+inline int check_frames(vx_ctx* c, const char* who, const vx_dmap* m, bool map_ok, uint64_t last_kf_id,
+                        const vx_frame* last_kf, const vx_frame* last, const vx_frame* curr, const double* intr4) {
+    if (!curr || !curr->block.p || !intr4) return set_error(c, VX_ERR_INVALID, "%s: null argument", who);
+    if (!last_kf && !last) return set_error(c, VX_ERR_INVALID, "%s: neither a last keyframe nor a last frame", who);
+    if (last_kf && !map_ok) return set_error(c, VX_ERR_INVALID, "%s: a last keyframe without a map / options", who);
+    for (const vx_frame* f : {last_kf, last, curr})
+        if (f && (!f->block.p || f->device != c->device))
+            return set_error(c, VX_ERR_INVALID, "%s: frame and context on different devices", who);
+    if (last_kf && m->kf_index.find(last_kf_id) == m->kf_index.end())
+        return set_error(c, VX_ERR_INVALID, "%s: keyframe %llu is not in the map", who, (unsigned long long)last_kf_id);
+    return VX_OK;
 }
 
 }  // namespace trk

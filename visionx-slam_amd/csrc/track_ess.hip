@@ -29,6 +29,9 @@
 // as PoseFromRt (host/src/geometry.cpp), the Hamilton product, the first-order renormalisation,
 // t = R(q_cl) t_lw + t_cl in SE3d::operator*(Vec3d)'s operation order (host/include/visionx/types.h)
 // — so the host adapters, tests/track_ess_ref.py and this kernel run the same IEEE sequence.
+//
+// Host side: EPairArgs / EPoseArgs are filled and the host values checked (trk::check_ess_host_args) by
+// track_bodies.hpp's host section; the host-input form stages its upload in c->te_in (vx::StagedUpload).
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -64,17 +67,6 @@ size_t packed_bytes(int cap) { return trk::packed_bytes<vx_track_essential_resul
 
 bool stride_ok(int64_t s) { return s >= 8 && !(s & 3); }
 
-// the checks on the host values both entry points make before anything touches a device
-int check_host_args(vx_ctx* c, const double* intr4, const vx_track_essential_options* opt) {
-    if (!intr4 || !opt) return set_error(c, VX_ERR_INVALID, "vx_track_essential: null intrinsics / options");
-    if (!(intr4[0] != 0.0 && intr4[1] != 0.0 && intr4[0] + intr4[1] != 0.0))
-        return set_error(c, VX_ERR_INVALID, "zero focal length");
-    if (opt->ess.max_iterations > 4096)
-        return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", opt->ess.max_iterations);
-    if (!(opt->ess.threshold >= 0.0)) return set_error(c, VX_ERR_INVALID, "bad essential options");
-    return VX_OK;
-}
-
 }  // namespace
 }  // namespace vx
 
@@ -97,7 +89,7 @@ int vx_track_essential_async(vx_ctx* c, const float* d_last_xy, int64_t last_str
     if (!d_last_xy || !d_n_last || !d_curr_xy || !d_n_curr)
         return set_error(c, VX_ERR_INVALID, "vx_track_essential_async: null argument");
     int rc;
-    if ((rc = check_host_args(c, intr4, opt))) return rc;
+    if ((rc = trk::check_ess_host_args(c, "vx_track_essential_async", intr4, opt))) return rc;
     if (!stride_ok(last_stride_bytes) || !stride_ok(curr_stride_bytes))
         return set_error(c, VX_ERR_INVALID, "position strides %lld / %lld: multiples of 4, at least 8",
                          (long long)last_stride_bytes, (long long)curr_stride_bytes);
@@ -115,10 +107,8 @@ int vx_track_essential_async(vx_ctx* c, const float* d_last_xy, int64_t last_str
     VX_HIP(c, c->te_good.ensure((size_t)cap * sizeof(int)));
     VX_HIP(c, c->te_p1.ensure((size_t)cap * 2 * sizeof(float)));
     VX_HIP(c, c->te_p2.ensure((size_t)cap * 2 * sizeof(float)));
-    VX_HIP(c, c->te_prob.ensure(16 + 4 * sizeof(double) + sizeof(vx_essential_options)));
+    VX_HIP(c, c->te_prob.ensure(trk::prob1_bytes<EPairArgs>()));
     VX_HIP(c, c->te_out.ensure(packed_bytes(cap)));
-    uint8_t* prob = c->te_prob.as<uint8_t>();
-    uint8_t* out = c->te_out.as<uint8_t>();
     EPairArgs a{};
     a.matches = d_matches;
     a.n_matches = d_n_matches;
@@ -129,18 +119,12 @@ int vx_track_essential_async(vx_ctx* c, const float* d_last_xy, int64_t last_str
     a.curr_xy = reinterpret_cast<const uint8_t*>(d_curr_xy);
     a.curr_stride = curr_stride_bytes;
     a.n_curr = d_n_curr;
-    a.min_matches = opt->min_matches;
-    a.ess = opt->ess;
-    for (int i = 0; i < 4; ++i) a.intr[i] = intr4[i];
+    trk::set_options(a, *opt, intr4);
     a.good = c->te_good.as<int>();
     a.p1 = c->te_p1.as<float>();
     a.p2 = c->te_p2.as<float>();
-    a.pair_match = reinterpret_cast<int*>(out + off_pair_match());
-    a.mask = out + off_mask(cap);
-    a.res = reinterpret_cast<vx_track_essential_result*>(out);
-    a.offsets = reinterpret_cast<int*>(prob);
-    a.intr_out = reinterpret_cast<double*>(prob + 16);
-    a.opt_out = reinterpret_cast<vx_essential_options*>(prob + 16 + 4 * sizeof(double));
+    trk::packed_outputs(a, c->te_out.as<uint8_t>(), cap);
+    trk::prob1_pointers(a, c->te_prob.as<uint8_t>());
     c->te_valid = false;
     VX_HIP(c, launch(c, kStTrackEPairs, k_track_epairs, dim3(1), dim3(kBlock), 0, c->stream, a));
     EmDeviceArgs d{};
@@ -154,10 +138,7 @@ int vx_track_essential_async(vx_ctx* c, const float* d_last_xy, int64_t last_str
     // the per-match grids are sized by the capacity: the pair count is known on the device only
     if ((rc = ess_enqueue(c, 1, std::max(1, opt->ess.max_iterations), cap, d, c->te_hyp))) return rc;
     EPoseArgs p{};
-    p.res = a.res;
-    p.pose_last[3] = 1.0;
-    if (pose_last7)
-        for (int i = 0; i < 7; ++i) p.pose_last[i] = pose_last7[i];
+    trk::epose_args(p, a.res, pose_last7);
     VX_HIP(c, launch(c, kStTrackEPose, k_track_epose, dim3(1), dim3(64), 0, c->stream, p));
     c->te_cap = cap;
     c->te_min_matches = opt->min_matches;
@@ -174,7 +155,7 @@ int vx_track_essential_host_async(vx_ctx* c, const uint8_t* last_desc, int n_las
     if (n_last < 0 || n_curr < 0 || (n_last && (!last_desc || !last_xy)) || (n_curr && (!curr_desc || !curr_xy)))
         return set_error(c, VX_ERR_INVALID, "vx_track_essential_host_async: bad descriptor / position arguments");
     int rc;
-    if ((rc = check_host_args(c, intr4, opt))) return rc;
+    if ((rc = trk::check_ess_host_args(c, "vx_track_essential_host_async", intr4, opt))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     // one staged block: {n_last, n_curr} | last rows | current rows | last positions | current positions.
     // The row capacities are rounded up to 256 as in vx_track_pnp_host_async (one launch configuration,
@@ -183,11 +164,8 @@ int vx_track_essential_host_async(vx_ctx* c, const uint8_t* last_desc, int n_las
     const size_t o_q = 16, o_t = o_q + (size_t)cap_q * 32, o_qxy = o_t + (size_t)cap_t * 32,
                  o_txy = o_qxy + (size_t)cap_q * 8, bytes = o_txy + (size_t)cap_t * 8;
     // (the one place this entry can block: until the previous call's upload has left the staging)
-    if (c->te_in_event) VX_HIP(c, hipEventSynchronize(c->te_in_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&c->te_in_event, hipEventDisableTiming));
-    VX_HIP(c, c->te_in_host.ensure(bytes));
-    VX_HIP(c, c->te_in.ensure(bytes));
-    uint8_t* h = static_cast<uint8_t*>(c->te_in_host.p);
+    VX_HIP(c, c->te_in.begin(bytes));
+    uint8_t* h = static_cast<uint8_t*>(c->te_in.host.p);
     const int32_t counts[4] = {n_last, n_curr, 0, 0};
     std::memcpy(h, counts, sizeof counts);
     // rows between the counts and the rounded capacities are not filled: every kernel stops at the
@@ -200,10 +178,9 @@ int vx_track_essential_host_async(vx_ctx* c, const uint8_t* last_desc, int n_las
         std::memcpy(h + o_t, curr_desc, (size_t)n_curr * 32);
         std::memcpy(h + o_txy, curr_xy, (size_t)n_curr * 8);
     }
-    VX_HIP(c, hipMemcpyAsync(c->te_in.p, h, bytes, hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(c->te_in_event, c->stream));
-    const uint8_t* d = c->te_in.as<uint8_t>();
-    const int32_t* dn = c->te_in.as<int32_t>();
+    VX_HIP(c, c->te_in.upload(bytes, c->stream));
+    const uint8_t* d = c->te_in.dev.as<uint8_t>();
+    const int32_t* dn = c->te_in.dev.as<int32_t>();
     if ((rc = vx_match_device_async(c, d + o_q, dn, cap_q, d + o_t, dn + 1, cap_t, ratio))) return rc;
     // the list just enqueued, named explicitly with the capacity it was enqueued with
     return vx_track_essential_async(c, reinterpret_cast<const float*>(d + o_qxy), 8, dn,

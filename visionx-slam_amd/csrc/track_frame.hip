@@ -30,6 +30,9 @@
 // bytes; the final kernel moves 464 B of records, 5 B a pair and 20 B a keypoint (about 50 KB at 2000
 // features).  Resources (-Rpass-analysis=kernel-resource-usage, gfx950): k_track_gate 10 VGPRs / 34 SGPRs,
 // k_track_final 28 VGPRs / 56 SGPRs; no LDS, no scratch.
+//
+// Host side: the block's layout is trk::FrameBlock (c->tf_blk), GateArgs / FinalArgs are filled and the frames
+// checked (trk::check_frames) by track_bodies.hpp's host section.
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -44,8 +47,6 @@ namespace {
 constexpr int kGateBlock = 64;
 constexpr int kFinalBlock = 256;
 constexpr int kFinalMaxWg = 64;
-
-using trk::align16;
 
 using trk::FinalArgs;
 using trk::GateArgs;
@@ -74,14 +75,10 @@ int vx_track_frame_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const vx_fr
                          const vx_frame* curr, float ratio, const double* pose_last7, const double* intr4,
                          const vx_track_options* pnp_opt, const vx_track_essential_options* ess_opt) {
     if (!c) return VX_ERR_INVALID;
-    if (!curr || !curr->block.p || !intr4 || !ess_opt) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: null argument");
-    if (!last_kf && !last) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: neither a last keyframe nor a last frame");
-    if (last_kf && (!m || !pnp_opt)) return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: a last keyframe without a map / options");
-    for (const vx_frame* f : {last_kf, last, curr})
-        if (f && (!f->block.p || f->device != c->device))
-            return set_error(c, VX_ERR_INVALID, "vx_track_frame_async: frame and context on different devices");
-    if (last_kf && m->kf_index.find(last_kf_id) == m->kf_index.end())
-        return set_error(c, VX_ERR_INVALID, "keyframe %llu is not in the map", (unsigned long long)last_kf_id);
+    const char* who = "vx_track_frame_async";
+    if (!ess_opt) return set_error(c, VX_ERR_INVALID, "%s: null argument", who);
+    int rc;
+    if ((rc = trk::check_frames(c, who, m, m && pnp_opt, last_kf_id, last_kf, last, curr, intr4))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     c->tf_valid = c->tf_fetched = false;
     c->tf_cap[0] = c->tf_cap[1] = 0;
@@ -102,7 +99,6 @@ int vx_track_frame_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const vx_fr
     vx_match* list1 = shared ? list0 : c->tf_matches[1].as<vx_match>();
     const float* curr_xy = &curr->kp()->x;
     const int64_t stride = (int64_t)sizeof(vx_keypoint);
-    int rc;
 
     // 1 + 2: Match(last_kf, curr) and TrackWithPnP's chain on it (:340-455)
     if (last_kf) {
@@ -114,14 +110,9 @@ int vx_track_frame_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const vx_fr
     }
     // 3: the decision of :269-273
     GateArgs g{};
-    g.pnp = last_kf ? c->tk_out.as<vx_track_result>() : nullptr;
-    g.min_matches = last_kf ? pnp_opt->min_matches : 0;
-    g.min_inliers = last_kf ? pnp_opt->min_inliers : 0;
-    g.n_last = last ? last->count() : nullptr;
-    g.cap_last = last ? last->cap : 0;
+    trk::gate_args(g, last_kf ? c->tk_out.as<vx_track_result>() : nullptr, pnp_opt, last, gate);
     g.n_matches0 = shared ? n0 : nullptr;
     g.n_matches1 = n1;
-    g.gate = gate;
     VX_HIP(c, launch(c, kStTrackGate, k_track_gate, dim3(1), dim3(kGateBlock), 0, c->stream, g));
     // 4 + 5: Match(last, curr) under the gated count and TrackLastFrame's chain on it (:287-325)
     if (!shared &&
@@ -132,35 +123,17 @@ int vx_track_frame_async(vx_ctx* c, vx_dmap* m, uint64_t last_kf_id, const vx_fr
                                        pose_last7, intr4, ess_opt)))
         return rc;
     // 6: the head and the packed block
-    const int tk_cap = last_kf ? c->tk_cap : 0, te_cap = c->te_cap;
+    const trk::FrameBlock blk{last_kf ? c->tk_cap : 0, c->te_cap, curr->cap};
+    VX_HIP(c, c->tf_out.ensure(blk.bytes(true)));
     FinalArgs f{};
-    f.tk = last_kf ? c->tk_out.as<uint8_t>() : nullptr;
-    f.tk_cap = tk_cap;
-    f.te = c->te_out.as<uint8_t>();
-    f.te_cap = te_cap;
-    f.gate = gate;
-    f.has_last = last ? 1 : 0;
-    f.ess_min_matches = ess_opt->min_matches;
-    f.ess_min_inliers = ess_opt->min_inliers;
-    f.kp = reinterpret_cast<const uint8_t*>(curr->kp());
-    f.n_kp = curr->count();
-    f.cap_kp = curr->cap;
-    f.o_pm0 = align16(sizeof(vx_track_frame_result));
-    f.o_mask0 = f.o_pm0 + align16((size_t)tk_cap * 4);
-    f.o_pm1 = f.o_mask0 + align16((size_t)tk_cap);
-    f.o_mask1 = f.o_pm1 + align16((size_t)te_cap * 4);
-    f.o_kp = f.o_mask1 + align16((size_t)te_cap);
-    const size_t bytes = f.o_kp + align16((size_t)curr->cap * sizeof(vx_keypoint));
-    VX_HIP(c, c->tf_out.ensure(bytes));
-    f.out = c->tf_out.as<uint8_t>();
+    trk::final_args(f, last_kf ? c->tk_out.as<uint8_t>() : nullptr, c->te_out.as<uint8_t>(), blk, gate, last != nullptr, *ess_opt,
+                    curr, c->tf_out.as<uint8_t>());
     const size_t items = ((size_t)curr->cap * sizeof(vx_keypoint)) / 16 + 1;
     const int grid = (int)std::min<size_t>(kFinalMaxWg, (items + kFinalBlock - 1) / kFinalBlock);
     VX_HIP(c, launch(c, kStTrackFinal, k_track_final, dim3(std::max(grid, 1)), dim3(kFinalBlock), 0, c->stream, f));
     c->tf_cap[0] = cap0;
     c->tf_cap[1] = cap1;
-    c->tf_pair_cap[0] = tk_cap;
-    c->tf_pair_cap[1] = te_cap;
-    c->tf_cap_kp = curr->cap;
+    c->tf_blk = blk;
     c->tf_list1_own = !shared;
     c->tf_valid = true;
     return VX_OK;
@@ -171,11 +144,8 @@ int vx_track_frame_fetch(vx_ctx* c, vx_track_frame_result* out, vx_keypoint* cur
     if (curr_kp && (!n_kp || cap_kp < 0)) return set_error(c, VX_ERR_INVALID, "vx_track_frame_fetch: keypoints without a count / capacity");
     if (!c->tf_valid) return set_error(c, VX_ERR_STATE, "no vx_track_frame_async enqueued");
     VX_HIP(c, hipSetDevice(c->device));
-    const size_t o_pm0 = align16(sizeof(vx_track_frame_result));
-    const size_t o_kp = o_pm0 + align16((size_t)c->tf_pair_cap[0] * 4) + align16((size_t)c->tf_pair_cap[0]) +
-                        align16((size_t)c->tf_pair_cap[1] * 4) + align16((size_t)c->tf_pair_cap[1]);
     // the keypoint rows are the block's tail: copied only when asked for
-    const size_t bytes = curr_kp ? o_kp + align16((size_t)c->tf_cap_kp * sizeof(vx_keypoint)) : o_kp;
+    const size_t o_kp = c->tf_blk.kp(), bytes = c->tf_blk.bytes(curr_kp != nullptr);
     VX_HIP(c, c->tf_host.ensure(bytes));
     VX_HIP(c, hipMemcpyAsync(c->tf_host.p, c->tf_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
     VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -195,16 +165,7 @@ int vx_track_frame_pairs(vx_ctx* c, int which, int32_t* pair_match, uint8_t* mas
     if (!c) return VX_ERR_INVALID;
     if (which != 0 && which != 1) return set_error(c, VX_ERR_INVALID, "vx_track_frame_pairs: path %d (0 or 1)", which);
     if (!c->tf_valid || !c->tf_fetched) return set_error(c, VX_ERR_STATE, "no vx_track_frame_fetch before vx_track_frame_pairs");
-    const uint8_t* h = static_cast<const uint8_t*>(c->tf_host.p);
-    const vx_track_frame_result* r = reinterpret_cast<const vx_track_frame_result*>(h);
-    const int np = which ? r->ess.n_pairs : r->pnp.n_pairs;
-    if ((pair_match || mask) && np > cap_pairs) return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
-    size_t o_pm = align16(sizeof(vx_track_frame_result));
-    if (which) o_pm += align16((size_t)c->tf_pair_cap[0] * 4) + align16((size_t)c->tf_pair_cap[0]);
-    const size_t o_mask = o_pm + align16((size_t)c->tf_pair_cap[which] * 4);
-    if (pair_match && np) std::memcpy(pair_match, h + o_pm, (size_t)np * 4);
-    if (mask && np) std::memcpy(mask, h + o_mask, (size_t)np);
-    return VX_OK;
+    return trk::copy_pairs(c, static_cast<const uint8_t*>(c->tf_host.p), c->tf_blk, which, pair_match, mask, cap_pairs);
 }
 
 int vx_track_frame_matches(vx_ctx* c, int which, const vx_match** d_matches, const int32_t** d_n, int32_t* cap) {

@@ -37,8 +37,9 @@
 //
 // The per-camera arguments (RigCam: five argument records, about 1 KB) do not fit kernel arguments 16
 // times over: one table is staged in pinned memory and uploaded in one copy per call, the staging
-// guarded by an event as in the *_host_async forms.  The kernels read their entry through uniform
-// addresses (scalar loads).
+// guarded by an event as in the *_host_async forms (c->tr_tab, vx::StagedUpload).  The kernels read their entry
+// through uniform addresses (scalar loads).  An entry is filled by the single call's fillers (track_bodies.hpp's host
+// section), which also state the checks, the block layout (trk::FrameBlock, tr_cam[i].blk) and the problem records.
 //
 // Every kernel is bound by launch latency at rig sizes (a camera's work is the single call's).
 // Resources (-Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / SGPRs / LDS / scratch):
@@ -55,8 +56,11 @@
 namespace vx {
 namespace {
 
-using trk::align16;
 using trk::kBlock;
+using trk::kProbCnt;
+using trk::kProbIntr;
+using trk::kProbOffsets;
+using trk::kProbOpt;
 
 constexpr int kPackBlock = 256;
 constexpr int kPackMaxWg = 16;
@@ -179,17 +183,6 @@ struct Carve {
     }
 };
 
-// problem records of one RANSAC: offsets[P + 1] | the cameras' {0, n} records | intr[4 P] | options[P]
-constexpr size_t kProbOffsets = 0, kProbCnt = 128, kProbIntr = 256, kProbOpt = 768;
-template <class Opt>
-constexpr size_t prob_bytes() { return kProbOpt + kP * sizeof(Opt); }
-static_assert((kP + 1) * sizeof(int) <= 128 && 2 * kP * sizeof(int) <= 128 && 4 * kP * sizeof(double) <= 512, "problem record");
-
-size_t part_bytes(int cp0, int cp1, int ckp) {
-    return align16(sizeof(vx_track_frame_result)) + align16((size_t)cp0 * 4) + align16((size_t)cp0) + align16((size_t)cp1 * 4) +
-           align16((size_t)cp1) + align16((size_t)ckp * sizeof(vx_keypoint));
-}
-
 int check_cam(vx_ctx* c, int cam, const char* what) {
     if (cam < 0 || cam >= c->tr_n) return set_error(c, VX_ERR_INVALID, "%s: camera %d outside [0, %d)", what, cam, c->tr_n);
     return VX_OK;
@@ -209,7 +202,7 @@ int vx_track_rig_layout(int n_cams, const int32_t* cap_pairs0, const int32_t* ca
     for (int i = 0; i < n_cams; ++i) {
         if (cap_pairs0[i] < 0 || cap_pairs1[i] < 0 || cap_kp[i] < 0) return VX_ERR_INVALID;
         if (cam_offset) cam_offset[i] = (int64_t)at;
-        at += part_bytes(cap_pairs0[i], cap_pairs1[i], cap_kp[i]);  // (a sum of multiples of 16)
+        at += trk::FrameBlock{cap_pairs0[i], cap_pairs1[i], cap_kp[i]}.bytes(true);  // (a sum of multiples of 16)
     }
     if (total_bytes) *total_bytes = (int64_t)at;
     return VX_OK;
@@ -222,35 +215,26 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
         return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: %d cameras outside [1, %d]", n_cams, VX_MAX_RIG_CAMERAS);
     if (!cams || !ess_opt) return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: null argument");
     // ---- vx_track_frame_async's checks (and those of the two calls it runs), camera by camera
+    const char* call = "vx_track_rig_async";
+    int rc;
     bool any_kf = false;
     for (int i = 0; i < n_cams; ++i) {
         const vx_rig_camera& k = cams[i];
-        if (!k.curr || !k.curr->block.p || !k.intr4) return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: camera %d: null argument", i);
-        if (!k.last_kf && !k.last)
-            return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: camera %d: neither a last keyframe nor a last frame", i);
-        if (k.last_kf && (!m || !m->c || !pnp_opt))
-            return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: camera %d: a last keyframe without a map / options", i);
-        for (const vx_frame* f : {k.last_kf, k.last, k.curr})
-            if (f && (!f->block.p || f->device != c->device))
-                return set_error(c, VX_ERR_INVALID, "vx_track_rig_async: camera %d: frame and context on different devices", i);
-        if (k.last_kf && m->kf_index.find(k.last_kf_id) == m->kf_index.end())
-            return set_error(c, VX_ERR_INVALID, "camera %d: keyframe %llu is not in the map", i, (unsigned long long)k.last_kf_id);
-        if (!(k.intr4[0] != 0.0 && k.intr4[1] != 0.0 && k.intr4[0] + k.intr4[1] != 0.0))
-            return set_error(c, VX_ERR_INVALID, "camera %d: zero focal length", i);
+        char who[48];
+        std::snprintf(who, sizeof who, "%s: camera %d", call, i);
+        if ((rc = trk::check_frames(c, who, m, m && m->c && pnp_opt, k.last_kf_id, k.last_kf, k.last, k.curr, k.intr4))) return rc;
+        if ((rc = trk::check_focal(c, who, k.intr4))) return rc;
         any_kf |= k.last_kf != nullptr;
     }
     if (any_kf) {
-        if (m->c->device != c->device) return set_error(c, VX_ERR_INVALID, "map and context on different devices");
-        if (pnp_opt->pnp.max_iterations > 4096) return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", pnp_opt->pnp.max_iterations);
-        if (pnp_opt->pnp.refine_iterations < 0 || !(pnp_opt->pnp.reproj_error >= 0.0)) return set_error(c, VX_ERR_INVALID, "bad PnP options");
+        if (m->c->device != c->device) return set_error(c, VX_ERR_INVALID, "%s: map and context on different devices", call);
+        if ((rc = trk::check_pnp_options(c, call, pnp_opt->pnp))) return rc;
     }
-    if (ess_opt->ess.max_iterations > 4096) return set_error(c, VX_ERR_INVALID, "max_iterations %d > 4096", ess_opt->ess.max_iterations);
-    if (!(ess_opt->ess.threshold >= 0.0)) return set_error(c, VX_ERR_INVALID, "bad essential options");
+    if ((rc = trk::check_ess_options(c, call, ess_opt->ess))) return rc;
     VX_HIP(c, hipSetDevice(c->device));
     // (as vx_track_frame_async: a call refused for its arguments leaves the previous call's result in place)
     c->tr_valid = c->tr_fetched = c->tr_fetched_kp = false;
     c->tr_n = 0;
-    int rc;
     if (any_kf) {  // as vx_track_pnp_async: the id table up to date on the map's stream, which this stream then follows
         if ((rc = ht_sync(m->c, m))) return set_error(c, rc, "landmark id table: %s", vx_last_error(m->c));
         if ((rc = vx_stream_wait_ctx(c, m->c))) return rc;
@@ -297,8 +281,8 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
     const size_t o_pkb = cw.take((size_t)slots * 2 * sizeof(float));
     const size_t o_mask0 = cw.take((size_t)slots);
     const size_t o_mask1 = cw.take((size_t)slots);
-    const size_t o_prob0 = cw.take(prob_bytes<vx_pnp_options>());
-    const size_t o_prob1 = cw.take(prob_bytes<vx_essential_options>());
+    const size_t o_prob0 = cw.take(trk::prob_bytes<trk::TrackArgs>());
+    const size_t o_prob1 = cw.take(trk::prob_bytes<trk::EPairArgs>());
     const size_t o_res0 = cw.take(kP * sizeof(vx_pnp_result));
     const size_t o_res1 = cw.take(kP * sizeof(vx_essential_result));
     size_t o_tk[kP], o_te[kP];
@@ -315,7 +299,6 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
     VX_HIP(c, c->tr_match.ensure(cm.at));
     VX_HIP(c, c->tr_work.ensure(cw.at));
     VX_HIP(c, c->tr_out.ensure((size_t)total));
-    VX_HIP(c, c->tr_tab.ensure(kP * sizeof(RigCam)));
     uint8_t* dm = c->tr_match.as<uint8_t>();
     uint8_t* dw = c->tr_work.as<uint8_t>();
     uint8_t* dout = c->tr_out.as<uint8_t>();
@@ -337,10 +320,8 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
     vx_essential_result* res1 = reinterpret_cast<vx_essential_result*>(dw + o_res1);
 
     // ---- the argument table, staged and uploaded in one copy
-    if (c->tr_tab_event) VX_HIP(c, hipEventSynchronize(c->tr_tab_event));
-    else VX_HIP(c, hipEventCreateWithFlags(&c->tr_tab_event, hipEventDisableTiming));
-    VX_HIP(c, c->tr_tab_host.ensure(kP * sizeof(RigCam)));
-    RigCam* tab = static_cast<RigCam*>(c->tr_tab_host.p);
+    VX_HIP(c, c->tr_tab.begin(kP * sizeof(RigCam)));
+    RigCam* tab = static_cast<RigCam*>(c->tr_tab.host.p);
     std::memset(tab, 0, (size_t)n_cams * sizeof(RigCam));
     const int64_t stride = (int64_t)sizeof(vx_keypoint);
     const uint8_t *mq0[kP], *mq1[kP], *mt[kP];
@@ -359,50 +340,35 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
         mnq1[i] = gate + 4 * i;
         mt[i] = k.curr->desc();
         mnt[i] = k.curr->count();
+        // what the fetches read of this camera (the call is not valid before its last launch is enqueued)
+        vx_ctx::RigCam& h = c->tr_cam[i];
+        h.cap[0] = cap0[i];
+        h.cap[1] = cap1[i];
+        h.blk = {pc0[i], pc1[i], ckp[i]};
+        h.list[0] = list0 + (size_t)i * q_cap0;
+        h.list[1] = list1 + (size_t)i * q_cap1;
+        h.count[0] = count0 + 4 * i;
+        h.count[1] = count1 + 4 * i;
+        h.offset = cam_off[i];
         // TrackWithPnP's pairs
         trk::TrackArgs& a = r.tk;
         if (k.last_kf) {
-            const int kf = m->kf_index.find(k.last_kf_id)->second;
             a.matches = list0 + (size_t)i * q_cap0;
             a.n_matches = count0 + 4 * i;
             a.cap_matches = cap0[i];
             a.curr_xy = curr_xy;
             a.stride = stride;
             a.n_curr = k.curr->count();
-            a.f0 = m->kf_feat_ptr[kf];
-            a.nf = (int)(m->kf_feat_ptr[kf + 1] - m->kf_feat_ptr[kf]);
-            a.feat_uv = m->feat_uv.as<double>();
-            a.feat_lm = m->feat_lm.as<uint64_t>();
-            a.feat_fl = m->feat_fl.as<uint8_t>();
-            a.ht_key = m->ht_key.as<uint64_t>();
-            a.ht_val = m->ht_val.as<int>();
-            a.ht_mask = m->ht_cap - 1;
-            a.lm_bad = m->lm_bad.as<uint8_t>();
-            a.lm_pos = m->lm_pos.as<double>();
+            trk::map_side(a, m, m->kf_index.find(k.last_kf_id)->second);
             a.good = good + seg0[i];
             a.obj = sega + 3 * seg0[i];
             a.img = segb + 2 * seg0[i];
-            a.pair_match = reinterpret_cast<int*>(tkb + trk::off_pair_match<vx_track_result>());
-            a.mask = tkb + trk::off_mask<vx_track_result>(pc0[i]);
-            a.res = reinterpret_cast<vx_track_result*>(tkb);
+            trk::packed_outputs(a, tkb, pc0[i]);
         }
-        a.min_matches = po.min_matches;
-        a.min_inliers = po.min_inliers;
-        a.pnp = po.pnp;
-        for (int j = 0; j < 4; ++j) a.intr[j] = k.intr4[j];
-        a.offsets = reinterpret_cast<int*>(prob0 + kProbCnt) + 2 * i;
-        a.intr_out = reinterpret_cast<double*>(prob0 + kProbIntr) + 4 * i;
-        a.opt_out = reinterpret_cast<vx_pnp_options*>(prob0 + kProbOpt) + i;
-        // the decision
-        trk::GateArgs& g = r.g;
-        g.pnp = k.last_kf ? reinterpret_cast<const vx_track_result*>(tkb) : nullptr;
-        g.min_matches = k.last_kf ? po.min_matches : 0;
-        g.min_inliers = k.last_kf ? po.min_inliers : 0;
-        g.n_last = k.last ? k.last->count() : nullptr;
-        g.cap_last = k.last ? k.last->cap : 0;
-        g.n_matches0 = nullptr;  // (last_kf == last: the fallback match runs again under the gate)
-        g.n_matches1 = nullptr;
-        g.gate = gate + 4 * i;
+        trk::set_options(a, po, k.intr4);
+        trk::prob_pointers(a, prob0, i);
+        // the decision (n_matches0 / n_matches1 stay NULL: with last_kf == last the fallback match runs again under the gate)
+        trk::gate_args(r.g, k.last_kf ? reinterpret_cast<const vx_track_result*>(tkb) : nullptr, &po, k.last, gate + 4 * i);
         // TrackLastFrame's pairs
         trk::EPairArgs& e = r.te;
         e.matches = list1 + (size_t)i * q_cap1;
@@ -414,46 +380,18 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
         e.curr_xy = curr_xy;
         e.curr_stride = stride;
         e.n_curr = k.curr->count();
-        e.min_matches = ess_opt->min_matches;
-        e.ess = ess_opt->ess;
-        for (int j = 0; j < 4; ++j) e.intr[j] = k.intr4[j];
+        trk::set_options(e, *ess_opt, k.intr4);
         e.good = good + seg1[i];
         e.p1 = sega + 2 * seg1[i];
         e.p2 = segb + 2 * seg1[i];
-        e.pair_match = reinterpret_cast<int*>(teb + trk::off_pair_match<vx_track_essential_result>());
-        e.mask = teb + trk::off_mask<vx_track_essential_result>(pc1[i]);
-        e.res = reinterpret_cast<vx_track_essential_result*>(teb);
-        e.offsets = reinterpret_cast<int*>(prob1 + kProbCnt) + 2 * i;
-        e.intr_out = reinterpret_cast<double*>(prob1 + kProbIntr) + 4 * i;
-        e.opt_out = reinterpret_cast<vx_essential_options*>(prob1 + kProbOpt) + i;
-        // T_cl * T_lw
-        r.ep.res = e.res;
-        r.ep.pose_last[3] = 1.0;
-        if (k.pose_last7)
-            for (int j = 0; j < 7; ++j) r.ep.pose_last[j] = k.pose_last7[j];
-        // the head and the packed block
-        trk::FinalArgs& f = r.f;
-        f.tk = k.last_kf ? tkb : nullptr;
-        f.tk_cap = pc0[i];
-        f.te = teb;
-        f.te_cap = pc1[i];
-        f.gate = gate + 4 * i;
-        f.has_last = k.last ? 1 : 0;
-        f.ess_min_matches = ess_opt->min_matches;
-        f.ess_min_inliers = ess_opt->min_inliers;
-        f.kp = reinterpret_cast<const uint8_t*>(k.curr->kp());
-        f.n_kp = k.curr->count();
-        f.cap_kp = ckp[i];
-        f.out = dout + cam_off[i];
-        f.o_pm0 = align16(sizeof(vx_track_frame_result));
-        f.o_mask0 = f.o_pm0 + align16((size_t)pc0[i] * 4);
-        f.o_pm1 = f.o_mask0 + align16((size_t)pc0[i]);
-        f.o_mask1 = f.o_pm1 + align16((size_t)pc1[i] * 4);
-        f.o_kp = f.o_mask1 + align16((size_t)pc1[i]);
+        trk::packed_outputs(e, teb, pc1[i]);
+        trk::prob_pointers(e, prob1, i);
+        // T_cl * T_lw; the head and the packed block
+        trk::epose_args(r.ep, e.res, k.pose_last7);
+        trk::final_args(r.f, k.last_kf ? tkb : nullptr, teb, h.blk, gate + 4 * i, k.last != nullptr, *ess_opt, k.curr, dout + cam_off[i]);
     }
-    VX_HIP(c, hipMemcpyAsync(c->tr_tab.p, tab, (size_t)n_cams * sizeof(RigCam), hipMemcpyHostToDevice, c->stream));
-    VX_HIP(c, hipEventRecord(c->tr_tab_event, c->stream));
-    const RigCam* dtab = c->tr_tab.as<RigCam>();
+    VX_HIP(c, c->tr_tab.upload((size_t)n_cams * sizeof(RigCam), c->stream));
+    const RigCam* dtab = c->tr_tab.dev.as<RigCam>();
 
     // ---- 1 + 2: Match(last_kf_i, curr_i) and TrackWithPnP's chain on all of them (:340-455)
     if ((rc = match_batch_enqueue_to(c, n_cams, mq0, mnq0, mt, mnt, q_cap0, t_cap, ratio, best, list0, count0))) return rc;
@@ -480,9 +418,7 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
     pd.img = pkb;
     pd.out = res0;
     pd.mask = dw + o_mask0;
-    // (the hypothesis grid is the host-side bound of the budget, as in vx_track_pnp_async)
-    const int hmax0 = std::max(1, po.pnp.max_iterations < 0 ? 100 : po.pnp.max_iterations);
-    if ((rc = pnp_enqueue(c, n_cams, hmax0, pd, c->tr_hyp[0]))) return rc;
+    if ((rc = pnp_enqueue(c, n_cams, trk::pnp_hyp_bound(po.pnp), pd, c->tr_hyp[0]))) return rc;
     // ---- 3: the decision of :269-273, per camera
     VX_HIP(c, launch(c, kStRigGate, k_rig_gate, dim3(1), dim3(64), 0, c->stream, dtab, n_cams, (const vx_pnp_result*)res0));
     // ---- 4 + 5: Match(last_i, curr_i) under the gated counts and TrackLastFrame's chain (:287-325)
@@ -512,19 +448,6 @@ int vx_track_rig_async(vx_ctx* c, vx_dmap* m, int n_cams, const vx_rig_camera* c
     VX_HIP(c, launch(c, kStRigFinal, k_rig_final, dim3(std::max(fgrid, 1), n_cams), dim3(kFinalBlock), 0, c->stream, dtab,
                      (const int*)(prob0 + kProbOffsets), (const uint8_t*)(dw + o_mask0), (const int*)(prob1 + kProbOffsets),
                      (const uint8_t*)(dw + o_mask1)));
-    for (int i = 0; i < n_cams; ++i) {
-        vx_ctx::RigCam& h = c->tr_cam[i];
-        h.cap[0] = cap0[i];
-        h.cap[1] = cap1[i];
-        h.pair_cap[0] = pc0[i];
-        h.pair_cap[1] = pc1[i];
-        h.cap_kp = ckp[i];
-        h.list[0] = list0 + (size_t)i * q_cap0;
-        h.list[1] = list1 + (size_t)i * q_cap1;
-        h.count[0] = count0 + 4 * i;
-        h.count[1] = count1 + 4 * i;
-        h.offset = cam_off[i];
-    }
     c->tr_n = n_cams;
     c->tr_bytes = total;
     c->tr_valid = true;
@@ -538,8 +461,7 @@ int vx_track_rig_fetch(vx_ctx* c, int with_keypoints, vx_track_frame_result* out
     VX_HIP(c, hipSetDevice(c->device));
     // the keypoint rows are each part's tail: without them the copy ends before the last part's
     const vx_ctx::RigCam& lastc = c->tr_cam[c->tr_n - 1];
-    const size_t bytes = with_keypoints ? (size_t)c->tr_bytes
-                                        : (size_t)lastc.offset + part_bytes(lastc.pair_cap[0], lastc.pair_cap[1], 0);
+    const size_t bytes = with_keypoints ? (size_t)c->tr_bytes : (size_t)lastc.offset + lastc.blk.bytes(false);
     VX_HIP(c, c->tr_host.ensure((size_t)c->tr_bytes));
     VX_HIP(c, hipMemcpyAsync(c->tr_host.p, c->tr_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
     VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -561,16 +483,7 @@ int vx_track_rig_pairs(vx_ctx* c, int cam, int which, int32_t* pair_match, uint8
     int rc;
     if ((rc = check_cam(c, cam, "vx_track_rig_pairs"))) return rc;
     const vx_ctx::RigCam& k = c->tr_cam[cam];
-    const uint8_t* h = static_cast<const uint8_t*>(c->tr_host.p) + k.offset;
-    const vx_track_frame_result* r = reinterpret_cast<const vx_track_frame_result*>(h);
-    const int np = which ? r->ess.n_pairs : r->pnp.n_pairs;
-    if ((pair_match || mask) && np > cap_pairs) return set_error(c, VX_ERR_CAPACITY, "need %d pairs, cap %d", np, cap_pairs);
-    size_t o_pm = align16(sizeof(vx_track_frame_result));
-    if (which) o_pm += align16((size_t)k.pair_cap[0] * 4) + align16((size_t)k.pair_cap[0]);
-    const size_t o_mask = o_pm + align16((size_t)k.pair_cap[which] * 4);
-    if (pair_match && np) std::memcpy(pair_match, h + o_pm, (size_t)np * 4);
-    if (mask && np) std::memcpy(mask, h + o_mask, (size_t)np);
-    return VX_OK;
+    return trk::copy_pairs(c, static_cast<const uint8_t*>(c->tr_host.p) + k.offset, k.blk, which, pair_match, mask, cap_pairs);
 }
 
 int vx_track_rig_keypoints(vx_ctx* c, int cam, vx_keypoint* kp, int cap, int* n) {
@@ -582,10 +495,10 @@ int vx_track_rig_keypoints(vx_ctx* c, int cam, vx_keypoint* kp, int cap, int* n)
     if ((rc = check_cam(c, cam, "vx_track_rig_keypoints"))) return rc;
     const vx_ctx::RigCam& k = c->tr_cam[cam];
     const uint8_t* h = static_cast<const uint8_t*>(c->tr_host.p) + k.offset;
-    const int nk = std::min(std::max(reinterpret_cast<const vx_track_frame_result*>(h)->n_keypoints, 0), k.cap_kp);
+    const int nk = std::min(std::max(reinterpret_cast<const vx_track_frame_result*>(h)->n_keypoints, 0), k.blk.cap_kp);
     *n = nk;
     if (kp && nk > cap) return set_error(c, VX_ERR_CAPACITY, "need %d keypoints, cap %d", nk, cap);
-    if (kp && nk) std::memcpy(kp, h + part_bytes(k.pair_cap[0], k.pair_cap[1], 0), (size_t)nk * sizeof(vx_keypoint));
+    if (kp && nk) std::memcpy(kp, h + k.blk.kp(), (size_t)nk * sizeof(vx_keypoint));
     return VX_OK;
 }
 
@@ -612,9 +525,9 @@ int vx_track_rig_block(vx_ctx* c, const uint8_t** block, int64_t* bytes, int32_t
     if (block) *block = static_cast<const uint8_t*>(c->tr_host.p);
     if (bytes) *bytes = c->tr_bytes;
     for (int i = 0; i < c->tr_n; ++i) {
-        if (cap_pairs0) cap_pairs0[i] = c->tr_cam[i].pair_cap[0];
-        if (cap_pairs1) cap_pairs1[i] = c->tr_cam[i].pair_cap[1];
-        if (cap_kp) cap_kp[i] = c->tr_cam[i].cap_kp;
+        if (cap_pairs0) cap_pairs0[i] = c->tr_cam[i].blk.cap0;
+        if (cap_pairs1) cap_pairs1[i] = c->tr_cam[i].blk.cap1;
+        if (cap_kp) cap_kp[i] = c->tr_cam[i].blk.cap_kp;
     }
     return VX_OK;
 }

@@ -251,7 +251,7 @@ void vx_destroy(vx_ctx* c) {
     if (c->snap_map) vx_dmap_destroy(c->snap_map);
     vx::plan_pool_release(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (auto e : {c->order_event, c->tk_in_event, c->te_in_event, c->ig_in_event, c->fr_in_event, c->tr_tab_event})
+    for (auto e : {c->order_event, c->fr_in_event})
         if (e) (void)hipEventDestroy(e);
 #ifndef VX_NO_RCCL
     if (c->comm) ncclCommDestroy(c->comm);

@@ -131,6 +131,43 @@ struct PinnedBuf {
     }
 };
 
+inline size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+// A host block staged in pinned memory and uploaded into a device block of its own in one copy, the
+// staging guarded by an event: begin() waits until the previous upload has left the staging (the one
+// place an entry that uses it can block) or creates the event, and ensures both blocks; the caller
+// fills host.p; upload() copies and records the event.
+struct StagedUpload {
+    PinnedBuf host;
+    DevBuf dev;
+    hipEvent_t event = nullptr;
+    ~StagedUpload() {
+        if (event) (void)hipEventDestroy(event);
+    }
+    hipError_t begin(size_t bytes) {
+        hipError_t e = event ? hipEventSynchronize(event) : hipEventCreateWithFlags(&event, hipEventDisableTiming);
+        if (e == hipSuccess) e = host.ensure(bytes);
+        if (e == hipSuccess) e = dev.ensure(bytes);
+        return e;
+    }
+    hipError_t upload(size_t bytes, hipStream_t stream) {
+        const hipError_t e = hipMemcpyAsync(dev.p, host.p, bytes, hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? hipEventRecord(event, stream) : e;
+    }
+};
+
+// Track()'s packed block (track_frame.hip, track_rig.hip) by its three capacities.  Declared here because
+// the context holds them by value; the members, the one statement of the layout, are in track_bodies.hpp.
+namespace trk {
+struct FrameBlock {
+    int cap0 = 0, cap1 = 0, cap_kp = 0;  // pair capacities of the two paths, keypoint rows
+    size_t pm(int which) const;          // offset of pair_match0 / pair_match1
+    size_t mask(int which) const;        // ... of mask0 / mask1
+    size_t kp() const;                   // ... of the keypoint rows
+    size_t bytes(bool with_keypoints) const;
+};
+}  // namespace trk
+
 // Host-computed geometry of one ORB configuration (image size + params).  Mirrors the layer
 // layout of ORB_Impl::detectAndCompute (levels stored unpadded, back to back).
 struct OrbGeometry {
@@ -258,9 +295,7 @@ struct vx_ctx {
     // above may run between vx_track_pnp_async and its fetch
     vx::DevBuf tk_good, tk_obj, tk_img, tk_prob, tk_hyp, tk_out;  // kept-match list, pairs, PnP record, packed result
     vx::PinnedBuf tk_host;
-    vx::PinnedBuf tk_in_host;    // vx_track_pnp_host_async: descriptors + positions staged for one upload ...
-    vx::DevBuf tk_in;            // ... into one device block
-    hipEvent_t tk_in_event = nullptr;  // (recorded after that upload: the staging is reused once it has passed)
+    vx::StagedUpload tk_in;      // vx_track_pnp_host_async: descriptors + positions staged for one upload
     int tk_cap = 0;              // match capacity of the enqueued call (sizes the packed result)
     int tk_min_matches = 0, tk_min_inliers = 0;
     bool tk_valid = false;
@@ -269,9 +304,7 @@ struct vx_ctx {
     // essential track and the RANSAC entry points may all be in flight together
     vx::DevBuf te_good, te_p1, te_p2, te_prob, te_hyp, te_out;  // kept-match list, pairs, essential record, packed result
     vx::PinnedBuf te_host;
-    vx::PinnedBuf te_in_host;    // vx_track_essential_host_async: descriptors + positions staged for one upload ...
-    vx::DevBuf te_in;            // ... into one device block
-    hipEvent_t te_in_event = nullptr;  // (recorded after that upload)
+    vx::StagedUpload te_in;      // vx_track_essential_host_async: descriptors + positions staged for one upload
     int te_cap = 0;              // match capacity of the enqueued call (sizes the packed result)
     int te_min_matches = 0, te_min_inliers = 0;
     bool te_valid = false;
@@ -279,9 +312,7 @@ struct vx_ctx {
     // ---- InitWithFirstFrame's gates on the device (init_gate.hip)
     vx::DevBuf ig_part, ig_out;  // per-workgroup {sum, sum_sq} slots, the result record
     vx::PinnedBuf ig_host;       // the fetched record
-    vx::PinnedBuf ig_in_host;    // vx_init_gate_host_async: count + positions + image rows staged for one upload ...
-    vx::DevBuf ig_in;            // ... into one device block
-    hipEvent_t ig_in_event = nullptr;  // (recorded after that upload)
+    vx::StagedUpload ig_in;      // vx_init_gate_host_async: count + positions + image rows staged for one upload
     bool ig_valid = false;
 
     // ---- device-resident frames (frame.hip): the pinned staging of vx_frame_extract_host_async (image
@@ -294,16 +325,13 @@ struct vx_ctx {
     vx::DevBuf tf_matches[2], tf_count, tf_gate, tf_out;  // tf_count: int32[8], list i's count at [4 * i]
     vx::PinnedBuf tf_host;
     int tf_cap[2] = {0, 0};      // match capacities of the enqueued call (0: that match was not enqueued)
-    int tf_pair_cap[2] = {0, 0}; // pair capacities of the two paths (size the packed block's pair arrays)
-    int tf_cap_kp = 0;           // keypoint rows the packed block holds
+    vx::trk::FrameBlock tf_blk;  // the packed block's pair capacities and keypoint rows
     bool tf_list1_own = true;    // false: list 1 is list 0's rows under a gated count (last_kf == last)
     bool tf_valid = false, tf_fetched = false;
 
     // ---- Track() for a rig (track_rig.hip): buffers of its own throughout, so a single-camera track
     // (tk_*, te_*, tf_*) may be in flight on the same context
-    vx::PinnedBuf tr_tab_host;   // the per-camera argument table, staged for one upload ...
-    vx::DevBuf tr_tab;           // ... into one device block
-    hipEvent_t tr_tab_event = nullptr;  // (recorded after that upload: the staging is reused once it has passed)
+    vx::StagedUpload tr_tab;     // the per-camera argument table, staged for one upload
     vx::DevBuf tr_match;         // match scratch, both lists of every camera, their counts, the gate records
     vx::DevBuf tr_zero;          // int32[4] of zeros: the query count of a camera without a last keyframe (never written)
     vx::DevBuf tr_work;          // kept-match lists, pair segments, contiguous RANSAC arrays + masks, problem
@@ -313,8 +341,7 @@ struct vx_ctx {
     vx::PinnedBuf tr_host;
     struct RigCam {
         int cap[2] = {0, 0};       // match capacities (0: list 0 not enqueued: no last keyframe)
-        int pair_cap[2] = {0, 0};  // pair capacities of the two paths
-        int cap_kp = 0;
+        vx::trk::FrameBlock blk;   // the camera's block: pair capacities of the two paths, keypoint rows
         const vx_match* list[2] = {nullptr, nullptr};
         const int32_t* count[2] = {nullptr, nullptr};
         int64_t offset = 0;        // of the camera's block in tr_out / tr_host

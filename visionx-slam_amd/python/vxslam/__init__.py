@@ -407,6 +407,19 @@ def track_rig_layout(cap_pairs0, cap_pairs1, cap_kp):
     return off[:len(a)].copy(), int(total.value)
 
 
+def track_frame_block(cap_pairs0, cap_pairs1, cap_kp):
+    """Offsets inside one camera's packed block (trk::FrameBlock, csrc/track_bodies.hpp): (pair_match0, mask0,
+    pair_match1, mask1, keypoint rows, bytes) for the two paths' pair capacities and the keypoint capacity;
+    every part begins on a 16-byte boundary"""
+    a16 = lambda x: (int(x) + 15) & ~15
+    o_pm0 = a16(TRACK_FRAME_RESULT_DTYPE.itemsize)
+    o_m0 = o_pm0 + a16(cap_pairs0 * 4)
+    o_pm1 = o_m0 + a16(cap_pairs0)
+    o_m1 = o_pm1 + a16(cap_pairs1 * 4)
+    o_kp = o_m1 + a16(cap_pairs1)
+    return o_pm0, o_m0, o_pm1, o_m1, o_kp, o_kp + a16(cap_kp * KEYPOINT_DTYPE.itemsize)
+
+
 def track_frame_options(min_matches=None, min_inliers=None, pnp=None, ess=None):
     """(TRACK_OPTIONS_DTYPE, TRACK_ESS_OPTIONS_DTYPE) for Context.track_frame_async: Tracking::Options'
     two gates (tracking.h:27-28) on both paths; pnp / ess: dicts of track_options /
@@ -899,16 +912,11 @@ class Context:
         off, total = track_rig_layout(cp0, cp1, ckp)
         assert total == nbytes.value
         raw = np.ctypeslib.as_array(C.cast(blk, C.POINTER(C.c_uint8)), shape=(total,))
-        a16 = lambda x: (int(x) + 15) & ~15
         out = []
         for i in range(b):
             o = int(off[i])
             res = raw[o:o + TRACK_FRAME_RESULT_DTYPE.itemsize].copy().view(TRACK_FRAME_RESULT_DTYPE)[0]
-            o_pm0 = o + a16(TRACK_FRAME_RESULT_DTYPE.itemsize)
-            o_m0 = o_pm0 + a16(cp0[i] * 4)
-            o_pm1 = o_m0 + a16(cp0[i])
-            o_m1 = o_pm1 + a16(cp1[i] * 4)
-            o_kp = o_m1 + a16(cp1[i])
+            o_pm0, o_m0, o_pm1, o_m1, o_kp = (o + x for x in track_frame_block(cp0[i], cp1[i], ckp[i])[:5])
             k0, k1, nk = int(res["pnp"]["n_pairs"]), int(res["ess"]["n_pairs"]), int(res["n_keypoints"])
             pairs = [(raw[opm:opm + 4 * k].copy().view(np.int32), raw[om:om + k].copy())
                      for opm, om, k in ((o_pm0, o_m0, k0), (o_pm1, o_m1, k1))]
