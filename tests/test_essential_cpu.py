@@ -7,14 +7,11 @@ The restatement is pinned by what holds independently of the hypothesis stream: 
 solutions satisfy the essential-matrix constraints and contain the true E on noise-free data,
 RANSAC + recoverPose recover ground truth under outliers, and the kept model / iteration count /
 masks re-derived in numpy (sampler, Sampson error, the sequential loop, cheirality) agree."""
-import math
-
 import numpy as np
 import pytest
 
+from ransac_cases import ess_loop, ess_stream, sample5 as _sample5, sampson as _sampson
 from vxslam import synth
-
-M64 = (1 << 64) - 1
 
 
 def _hat(v):
@@ -27,40 +24,6 @@ def _norm(d):
     p2 = d["pts_curr"].astype(np.float64)
     return (np.stack([(p1[:, 0] - cx) / fx, (p1[:, 1] - cy) / fy], -1),
             np.stack([(p2[:, 0] - cx) / fx, (p2[:, 1] - cy) / fy], -1))
-
-
-def _mix(x):
-    x = (x + 0x9E3779B97F4A7C15) & M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
-def _sample5(seed, h, n):
-    idx = []
-    for a in range(64):
-        i = ((_mix((seed + h * 64 + a) & M64) >> 32) * n) >> 32
-        if i not in idx:
-            idx.append(i)
-        if len(idx) == 5:
-            return idx
-    return None
-
-
-def _sampson(E, x1, x2):
-    Ex1 = x1 @ E[:, :2].T + E[:, 2]
-    Etx2 = x2 @ E[:2, :] + E[2, :]
-    x2tEx1 = x2[:, 0] * Ex1[:, 0] + x2[:, 1] * Ex1[:, 1] + Ex1[:, 2]
-    return x2tEx1 ** 2 / (Ex1[:, 0] ** 2 + Ex1[:, 1] ** 2 + Etx2[:, 0] ** 2 + Etx2[:, 1] ** 2)
-
-
-def _update5(p, ep, max_iters):
-    num = max(1.0 - p, 2.2250738585072014e-308)
-    denom = 1.0 - (1.0 - ep) ** 5
-    if denom < 2.2250738585072014e-308:
-        return 0
-    num, denom = math.log(num), math.log(denom)
-    return max_iters if denom >= 0 or -num >= max_iters * -denom else int(np.rint(num / denom))
 
 
 def test_five_point_constraints_and_truth(oracle):
@@ -113,21 +76,11 @@ def test_loop_replay_and_masks(oracle):
         r, mask = oracle.essential_ransac(d["pts_last"], d["pts_curr"], d["intr"], o)
         x1, x2 = _norm(d)
         thr = 1.0 / ((d["intr"][0] + d["intr"][1]) * 0.5)
-        niters, best, good, h = H, None, 0, 0
-        models = {}
-        while h < niters:
-            idx = _sample5(int(o["seed"]), h, n)
-            Es = oracle.five_point(x1[idx], x2[idx])
-            for m, E in enumerate(Es):
-                c = int((_sampson(E, x1, x2) <= thr * thr).sum())
-                if c > max(good, 4):
-                    best, good = (h, m), c
-                    models[(h, m)] = E
-                    niters = _update5(0.999, (n - c) / n, niters)
-            h += 1
+        best, h, good, _ = ess_loop(ess_stream(oracle, d, int(o["seed"]), H), n, 0.999, H)
         assert (r["best_hypothesis"], r["best_model"]) == best
         assert r["hypotheses_run"] == h and r["n_ransac_inliers"] == good
-        E = models[best]
+        idx = _sample5(int(o["seed"]), best[0], n)
+        E = oracle.five_point(x1[idx], x2[idx])[best[1]]
         assert np.array_equal(r["E"].reshape(3, 3), E)
         ransac = _sampson(E, x1, x2) <= thr * thr
         assert np.array_equal(mask.astype(bool), mask.astype(bool) & ransac)

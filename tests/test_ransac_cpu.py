@@ -14,6 +14,7 @@ import math
 import numpy as np
 import pytest
 
+from ransac_cases import pnp_loop, update_iters
 from vxslam import synth
 
 
@@ -33,14 +34,7 @@ def _inliers(R, t, d, thr):
 
 def _update_iters(p, ep, max_iters):
     """RANSACUpdateNumIters (OpenCV calib3d ptsetreg.cpp), modelPoints = 4."""
-    p = min(max(p, 0.0), 1.0)
-    ep = min(max(ep, 0.0), 1.0)
-    num = max(1.0 - p, 2.2250738585072014e-308)
-    denom = 1.0 - (1.0 - ep) ** 4
-    if denom < 2.2250738585072014e-308:
-        return 0
-    num, denom = math.log(num), math.log(denom)
-    return max_iters if denom >= 0 or -num >= max_iters * -denom else int(np.rint(num / denom))
+    return update_iters(p, ep, max_iters, 4)
 
 
 def test_poly_roots_match_numpy(oracle):
@@ -113,13 +107,7 @@ def test_mask_and_loop_replay(oracle):
         for h in range(H):
             m = oracle.pnp_hypothesis(d["obj"], d["img"], d["intr"], int(o["seed"]), h)
             counts.append(None if m is None else int(_inliers(m[0], m[1], d, 2.0).sum()))
-        niters, best, good, h = H, -1, 0, 0
-        while h < niters:
-            c = counts[h]
-            if c is not None and c > max(good, 3):
-                best, good = h, c
-                niters = _update_iters(0.99, (n - c) / n, niters)
-            h += 1
+        best, h, good, _ = pnp_loop(counts, n, 0.99, H)
         assert r["best_hypothesis"] == best and r["hypotheses_run"] == h and r["n_inliers"] == good
         assert r["ok"] == (best >= 0)
         if best >= 0:

@@ -784,15 +784,19 @@ __device__ __forceinline__ bool cheirality(const double* R, const double* t, con
 // RANSACPointSetRegistrator::run replayed by wave 0 over the (hypothesis, model) records in
 // order, 64 at a time (in-wave prefix max + ballot finds the entries that beat every earlier
 // count and 4; the budget test applies when a new hypothesis starts, as in the sequential loop).
+// A hypothesis whose ten slots cross a block boundary (h = 6, 12, 19, ...) may shrink the budget to
+// <= h with a record in its first block: the sequential loop still scores its remaining models, so
+// the block loop goes on while a block can hold models of last_h, the last hypothesis started, and
+// loads those even at h >= niters.  last_h < min(H, hlimit): at most H * kMaxModels / 64 rounds.
 __device__ int4 replay(const EmRec* rec, int H, int n, double confidence, int hlimit = kMaxHyp,
                        int* budget = nullptr) {
     const int lane = threadIdx.x & 63;
     int niters = n >= 5 ? H : 0, best = -1, good = 0, last_h = -1;
     bool stop = false;
-    for (int base = 0; !stop && base < min(niters, hlimit) * kMaxModels; base += 64) {
+    for (int base = 0; !stop && base < max(min(niters, hlimit), last_h + 1) * kMaxModels; base += 64) {
         const int f = base + lane;
         const int h = f / kMaxModels, m = f - h * kMaxModels;
-        const int c = h < niters && h < hlimit ? rec[h].count[m] : -1;
+        const int c = (h < niters || h == last_h) && h < hlimit ? rec[h].count[m] : -1;
         int incl = c;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
