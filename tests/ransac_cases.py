@@ -1,9 +1,9 @@
-"""Cases that place the two RANSAC loop replays (replay() in csrc/ransac.hip and csrc/essential.hip)
-and the essential gate (k_em_gate) in every situation their block structure distinguishes, plus the
-plain references they are held to.  Shared by tests/test_ransac_replay_cpu.py and
-tests/test_gpu_ransac_replay.py; no GPU import.
+"""Cases that place the two RANSAC loop replays (the one replay() of csrc/ransac_common.hpp, with one
+model per hypothesis in csrc/ransac.hip and ten in csrc/essential.hip) and the essential gate (k_em_gate)
+in every situation their block structure distinguishes, plus the plain references they are held to.
+Shared by tests/test_ransac_replay_cpu.py and tests/test_gpu_ransac_replay.py; no GPU import.
 
-Both kernels turn RANSACPointSetRegistrator::run's sequential loop into blocks of 64 records: a prefix
+Both uses turn RANSACPointSetRegistrator::run's sequential loop into blocks of 64 records: a prefix
 max and a ballot find the entries that beat every earlier count, the ballot bits are walked in order
 and each shrinks the budget (RANSACUpdateNumIters).  PnP has one record per hypothesis (block =
 h // 64, lane = h % 64); the essential replay flattens (hypothesis, model) to f = 10 h + m, so the
@@ -300,7 +300,7 @@ def gate_value(rows, n, confidence, H):
 
 
 def ess_block_loop(rows, n, confidence, H, fixed, hlimit=MAX_HYP):
-    """essential.hip's replay() lane by lane on the CPU: blocks of 64 flattened records, an exclusive
+    """ransac_common.hpp's replay() with essential.hip's ten models lane by lane on the CPU: blocks of 64 flattened records, an exclusive
     prefix max, the ballot of the entries above it, the walk over the ballot bits.  fixed=False is the
     loop as it was (it ends as soon as base >= min(budget, hlimit) * 10 and loads no entry of a
     hypothesis at or beyond the budget); fixed=True goes on while the block can still hold models of

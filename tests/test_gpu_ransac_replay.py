@@ -1,5 +1,5 @@
-"""GPU parity of the two RANSAC loop replays (replay() of csrc/ransac.hip in k_pnp_refine, replay() of
-csrc/essential.hip in k_em_gate / k_em_pick) in every situation tests/ransac_cases.py commits a case
+"""GPU parity of the two RANSAC loop replays (replay() of csrc/ransac_common.hpp with one model per
+hypothesis in k_pnp_refine, with ten in k_em_gate / k_em_pick) in every situation tests/ransac_cases.py commits a case
 for, of the essential gate (a case alone = one k_em_hyp launch, the same case in a padded batch = two,
 byte-equal), of RANSACUpdateNumIters with the device log / rint against mpmath at 50 digits, and of
 runs that follow a longer one through the same context (records beyond a problem's budget are stale).

@@ -1,6 +1,7 @@
 """The cases of tests/ransac_cases.py are what they claim, on the CPU: every committed case realises its
 situation (classifier over the reference count stream), the oracle's loop equals the plain Python loop
-on it, the straddle cases tell the old block loop of csrc/essential.hip from the fixed one, and the
+on it, the straddle cases tell the old block loop (csrc/essential.hip's, before the fix) from the fixed
+one (now replay() of csrc/ransac_common.hpp), and the
 budget-formula sweep has the margin and the share of usable cases that tests/test_gpu_ransac_replay.py
 relies on (RANSACUpdateNumIters against mpmath at 50 digits)."""
 import numpy as np

@@ -17,18 +17,12 @@
 // the specification; -ffp-contract=off), so models, counts, the kept model, R, t and both masks are
 // bit-identical to it.  The (R, -t) candidates reuse the (R, t) triangulation with w negated — the
 // Jacobi rotations are odd in that column, so this is exactly what triangulating them gives.
-#include <algorithm>
-#include <cfloat>
-#include <cmath>
-#include <cstring>
-
-#include "vx_internal.hpp"
+#include "ransac_common.hpp"
 
 namespace vx {
 namespace {
 
 constexpr int kThreads = 64;  // one wave per hypothesis: the five-point solve is wave-parallel
-constexpr int kMaxHyp = 4096;
 constexpr int kMaxModels = 10;
 
 struct EmRec {
@@ -38,23 +32,10 @@ struct EmRec {
 };
 
 struct EmArgs {
-    const int* offsets;                // P + 1
-    const double* intr;                // 4 per problem
-    const vx_essential_options* opt;   // per problem
-    const float* p1;                   // 2 per match (pts_last)
-    const float* p2;                   // 2 per match (pts_curr)
-    EmRec* rec;                        // [P][hmax]
+    EmDeviceArgs d;
+    EmRec* rec;  // [P][hmax]
     int hmax;
-    vx_essential_result* out;          // per problem
-    uint8_t* mask;                     // per match
 };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 template <class T>
 __device__ __forceinline__ void swp(T& a, T& b) {
@@ -580,20 +561,6 @@ __device__ __forceinline__ double sampson(const double* E, double x1, double y1,
     return x2tEx1 * x2tEx1 / (a + b);
 }
 
-__device__ int update_num_iters5(double p, double ep, int max_iters) {
-    p = fmax(p, 0.0);
-    p = fmin(p, 1.0);
-    ep = fmax(ep, 0.0);
-    ep = fmin(ep, 1.0);
-    double num = fmax(1.0 - p, DBL_MIN);
-    const double x = 1.0 - ep;
-    double denom = 1.0 - ((x * x) * (x * x)) * x;
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0.0 || -num >= (double)max_iters * -denom ? max_iters : (int)rint(num / denom);
-}
-
 // normalised coordinates of match i (findEssentialMat / recoverPose with a camera matrix)
 __device__ __forceinline__ void norm_pts(const float* p1, const float* p2, int i, const double* K, double* q) {
     q[0] = ((double)p1[2 * i] - K[2]) / K[0];
@@ -602,38 +569,24 @@ __device__ __forceinline__ void norm_pts(const float* p1, const float* p2, int i
     q[3] = ((double)p2[2 * i + 1] - K[3]) / K[1];
 }
 
-__device__ __forceinline__ void block_count(int flag, int* lds_cnt) {
-    const uint64_t b = __ballot(flag);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(lds_cnt, __popcll(b));
-}
-
 __global__ void __launch_bounds__(kThreads) k_em_hyp(EmArgs a, int h0, const int* gate) {
     const int p = blockIdx.y, h = h0 + blockIdx.x, lane = threadIdx.x;
-    const vx_essential_options o = a.opt[p];
-    const int H = min(max(o.max_iterations, 0), kMaxHyp);
-    if (h >= H || (gate && h >= gate[p])) return;
-    const int b = a.offsets[p], n = a.offsets[p + 1] - b;
-    const float* p1 = a.p1 + 2 * (size_t)b;
-    const float* p2 = a.p2 + 2 * (size_t)b;
-    const double K[4] = {a.intr[4 * p], a.intr[4 * p + 1], a.intr[4 * p + 2], a.intr[4 * p + 3]};
+    const vx_essential_options o = a.d.opt[p];
+    if (h >= rs::hyp_budget(o.max_iterations, a.hmax) || (gate && h >= gate[p])) return;
+    const int b = a.d.offsets[p], n = a.d.offsets[p + 1] - b;
+    const float* p1 = a.d.p1 + 2 * (size_t)b;
+    const float* p2 = a.d.p2 + 2 * (size_t)b;
+    const double K[4] = {a.d.intr[4 * p], a.d.intr[4 * p + 1], a.d.intr[4 * p + 2], a.d.intr[4 * p + 3]};
     __shared__ FpWork w;
     __shared__ double sE[kMaxModels * 9];
     __shared__ int sgot, scnt[kMaxModels];
     if (lane < kMaxModels) scnt[lane] = 0;
     if (lane == 0) {
         int idx[5];
-        int got = 0;
-        if (n >= 5) {
-            for (int at = 0; at < 64 && got < 5; ++at) {
-                const uint64_t x = mix64(o.seed + (uint64_t)h * 64u + (uint64_t)at);
-                const int i = (int)(((x >> 32) * (uint64_t)n) >> 32);
-                bool dup = false;
-                for (int k = 0; k < got; ++k) dup |= idx[k] == i;
-                if (!dup) idx[got++] = i;
-            }
-        }
-        if (got == 5) {
+        const bool got = n >= 5 && rs::draw_distinct(o.seed, h, n, idx);
+        if (got) {
             double q[4];
+#pragma unroll
             for (int k = 0; k < 5; ++k) {
                 norm_pts(p1, p2, idx[k], K, q);
                 w.s1[2 * k] = q[0];
@@ -645,7 +598,7 @@ __global__ void __launch_bounds__(kThreads) k_em_hyp(EmArgs a, int h0, const int
         sgot = got;
     }
     WSYNC;
-    const int nm = sgot == 5 ? five_point_wave(w, sE, lane) : 0;
+    const int nm = sgot ? five_point_wave(w, sE, lane) : 0;
     const double thr = o.threshold / ((K[0] + K[1]) * 0.5);
     const double thr2 = thr * thr;
     for (int i0 = 0; i0 < n && nm > 0; i0 += kThreads) {
@@ -653,7 +606,7 @@ __global__ void __launch_bounds__(kThreads) k_em_hyp(EmArgs a, int h0, const int
         double q[4] = {0.0, 0.0, 0.0, 0.0};
         if (i < n) norm_pts(p1, p2, i, K, q);
         for (int m = 0; m < nm; ++m)
-            block_count(i < n && sampson(sE + 9 * m, q[0], q[1], q[2], q[3]) <= thr2, &scnt[m]);
+            rs::block_count(i < n && sampson(sE + 9 * m, q[0], q[1], q[2], q[3]) <= thr2, &scnt[m]);
     }
     WSYNC;
     EmRec* r = a.rec + (size_t)p * a.hmax + h;
@@ -781,50 +734,8 @@ __device__ __forceinline__ bool cheirality(const double* R, const double* t, con
     return z2 > 0.0 && z2 < dist;
 }
 
-// RANSACPointSetRegistrator::run replayed by wave 0 over the (hypothesis, model) records in
-// order, 64 at a time (in-wave prefix max + ballot finds the entries that beat every earlier
-// count and 4; the budget test applies when a new hypothesis starts, as in the sequential loop).
-// A hypothesis whose ten slots cross a block boundary (h = 6, 12, 19, ...) may shrink the budget to
-// <= h with a record in its first block: the sequential loop still scores its remaining models, so
-// the block loop goes on while a block can hold models of last_h, the last hypothesis started, and
-// loads those even at h >= niters.  last_h < min(H, hlimit): at most H * kMaxModels / 64 rounds.
-__device__ int4 replay(const EmRec* rec, int H, int n, double confidence, int hlimit = kMaxHyp,
-                       int* budget = nullptr) {
-    const int lane = threadIdx.x & 63;
-    int niters = n >= 5 ? H : 0, best = -1, good = 0, last_h = -1;
-    bool stop = false;
-    for (int base = 0; !stop && base < max(min(niters, hlimit), last_h + 1) * kMaxModels; base += 64) {
-        const int f = base + lane;
-        const int h = f / kMaxModels, m = f - h * kMaxModels;
-        const int c = (h < niters || h == last_h) && h < hlimit ? rec[h].count[m] : -1;
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(incl, off);
-            if (lane >= off) incl = max(incl, y);
-        }
-        int excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = -1;
-        uint64_t bits = __ballot(c > max(max(excl, good), 4));
-        while (bits) {
-            const int k = __ffsll((unsigned long long)bits) - 1;
-            const int fk = base + k, hk = fk / kMaxModels;
-            if (hk != last_h && hk >= niters) {
-                stop = true;
-                break;
-            }
-            const int ck = __shfl(c, k);
-            best = fk;
-            last_h = hk;
-            good = ck;
-            niters = update_num_iters5(confidence, (double)(n - ck) / (double)n, niters);
-            bits &= bits - 1;
-        }
-    }
-    const int hb = best >= 0 ? best / kMaxModels : -1;
-    if (budget) *budget = stop ? 0 : niters;
-    return make_int4(hb, best >= 0 ? best - hb * kMaxModels : -1, best >= 0 ? max(niters, hb + 1) : niters, good);
-}
+// The loop replay is rs::replay (ransac_common.hpp) over the ten count slots of each hypothesis
+// record, so the hypotheses h = 6, 12, 19, ... straddle a 64-slot block boundary (the rule is there).
 
 // k_em_gate: after the first kFirstChunk hypotheses, the budget the sequential loop has left
 // (RANSACUpdateNumIters only shrinks it): later hypotheses at or beyond it are never evaluated, so
@@ -832,11 +743,13 @@ __device__ int4 replay(const EmRec* rec, int H, int n, double confidence, int hl
 constexpr int kFirstChunk = 128;
 __global__ void __launch_bounds__(64) k_em_gate(EmArgs a, int* gate) {
     const int p = blockIdx.x;
-    const vx_essential_options o = a.opt[p];
-    const int H = min(max(o.max_iterations, 0), kMaxHyp);
-    const int n = a.offsets[p + 1] - a.offsets[p];
+    const vx_essential_options o = a.d.opt[p];
+    const int H = rs::hyp_budget(o.max_iterations, a.hmax);
+    const int n = a.d.offsets[p + 1] - a.d.offsets[p];
+    const EmRec* rec = a.rec + (size_t)p * a.hmax;
     int budget = 0;
-    replay(a.rec + (size_t)p * a.hmax, H, n, o.confidence, kFirstChunk, &budget);
+    rs::replay<kMaxModels, 5>([rec](int h, int m) { return rec[h].count[m]; }, H, n, o.confidence, kFirstChunk,
+                              &budget);
     if (threadIdx.x == 0) gate[p] = budget <= kFirstChunk ? 0 : budget;
 }
 
@@ -850,12 +763,12 @@ struct EmState {
 // k_em_pick: one wave per problem — the loop replay, the kept E, its decomposition
 __global__ void __launch_bounds__(64) k_em_pick(EmArgs a, EmState* st) {
     const int p = blockIdx.x;
-    const vx_essential_options o = a.opt[p];
-    const int H = min(max(o.max_iterations, 0), kMaxHyp);
-    const int n = a.offsets[p + 1] - a.offsets[p];
+    const vx_essential_options o = a.d.opt[p];
+    const int H = rs::hyp_budget(o.max_iterations, a.hmax);
+    const int n = a.d.offsets[p + 1] - a.d.offsets[p];
     const EmRec* rec = a.rec + (size_t)p * a.hmax;
     EmState* s = st + p;
-    const int4 r = replay(rec, H, n, o.confidence);
+    const int4 r = rs::replay<kMaxModels, 5>([rec](int h, int m) { return rec[h].count[m]; }, H, n, o.confidence);
     if (threadIdx.x < 4) s->cnt[threadIdx.x] = 0;
     if (threadIdx.x != 0) return;
     s->h = r.x;
@@ -892,11 +805,11 @@ __global__ void __launch_bounds__(kThreads * 4) k_em_cheir(EmArgs a, const EmSta
     const int p = blockIdx.y;
     const EmState* s = st + p;
     if (s->h < 0) return;
-    const int b = a.offsets[p], n = a.offsets[p + 1] - b;
+    const int b = a.d.offsets[p], n = a.d.offsets[p + 1] - b;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (blockIdx.x * blockDim.x >= n) return;
-    const vx_essential_options o = a.opt[p];
-    const double K[4] = {a.intr[4 * p], a.intr[4 * p + 1], a.intr[4 * p + 2], a.intr[4 * p + 3]};
+    const vx_essential_options o = a.d.opt[p];
+    const double K[4] = {a.d.intr[4 * p], a.d.intr[4 * p + 1], a.d.intr[4 * p + 2], a.d.intr[4 * p + 3]};
     const double thr = o.threshold / ((K[0] + K[1]) * 0.5);
     const double thr2 = thr * thr;
     __shared__ int scnt[4];
@@ -905,7 +818,7 @@ __global__ void __launch_bounds__(kThreads * 4) k_em_cheir(EmArgs a, const EmSta
     bool f[4] = {false, false, false, false};
     if (i < n) {
         double q[4], E[9];
-        norm_pts(a.p1 + 2 * (size_t)b, a.p2 + 2 * (size_t)b, i, K, q);
+        norm_pts(a.d.p1 + 2 * (size_t)b, a.d.p2 + 2 * (size_t)b, i, K, q);
         for (int k = 0; k < 9; ++k) E[k] = s->E[k];
         const bool in = sampson(E, q[0], q[1], q[2], q[3]) <= thr2;
         int flags = in ? 1 : 0;
@@ -924,9 +837,9 @@ __global__ void __launch_bounds__(kThreads * 4) k_em_cheir(EmArgs a, const EmSta
             }
             for (int k = 0; k < 4; ++k) flags |= f[k] ? 2 << k : 0;
         }
-        a.mask[b + i] = (uint8_t)flags;
+        a.d.mask[b + i] = (uint8_t)flags;
     }
-    for (int k = 0; k < 4; ++k) block_count(f[k], &scnt[k]);
+    for (int k = 0; k < 4; ++k) rs::block_count(f[k], &scnt[k]);
     __syncthreads();
     if (threadIdx.x < 4 && scnt[threadIdx.x]) atomicAdd(const_cast<int*>(&s->cnt[threadIdx.x]), scnt[threadIdx.x]);
 }
@@ -942,12 +855,12 @@ __device__ __forceinline__ int pick_candidate(const int* g) {
 __global__ void __launch_bounds__(kThreads * 4) k_em_final(EmArgs a, const EmState* st) {
     const int p = blockIdx.y;
     const EmState* s = st + p;
-    const int b = a.offsets[p], n = a.offsets[p + 1] - b;
+    const int b = a.d.offsets[p], n = a.d.offsets[p + 1] - b;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     int g[4];
     for (int k = 0; k < 4; ++k) g[k] = s->cnt[k];
     const int sel = pick_candidate(g);
-    if (i < n) a.mask[b + i] = s->h >= 0 && (a.mask[b + i] & (2 << sel)) ? 1 : 0;
+    if (i < n) a.d.mask[b + i] = s->h >= 0 && (a.d.mask[b + i] & (2 << sel)) ? 1 : 0;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     vx_essential_result z{};
     z.best_hypothesis = s->h;
@@ -967,10 +880,8 @@ __global__ void __launch_bounds__(kThreads * 4) k_em_final(EmArgs a, const EmSta
         }
         for (int k = 0; k < 3; ++k) z.t[k] = sel >= 2 ? -s->t[k] : s->t[k];
     }
-    a.out[p] = z;
+    a.d.out[p] = z;
 }
-
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -978,16 +889,7 @@ int ess_enqueue(vx_ctx* c, int P, int hmax, int n_bound, const EmDeviceArgs& d, 
     hmax = std::max(hmax, 1);
     const size_t rec_bytes = align16((size_t)P * hmax * sizeof(EmRec));
     VX_HIP(c, hyp.ensure(rec_bytes + (size_t)P * (sizeof(EmState) + sizeof(int))));
-    EmArgs a{};
-    a.offsets = d.offsets;
-    a.intr = d.intr;
-    a.opt = d.opt;
-    a.p1 = d.p1;
-    a.p2 = d.p2;
-    a.rec = hyp.as<EmRec>();
-    a.hmax = hmax;
-    a.out = d.out;
-    a.mask = d.mask;
+    const EmArgs a{d, hyp.as<EmRec>(), hmax};
     int* gate = reinterpret_cast<int*>(hyp.as<uint8_t>() + rec_bytes + (size_t)P * sizeof(EmState));
     // everything at once while the whole hypothesis grid is resident at the same time (8 one-wave
     // workgroups per CU at this kernel's register count); beyond that, gate by the remaining budget
@@ -1030,64 +932,21 @@ void vx_essential_default_options(vx_essential_options* o) {
 int vx_essential_ransac_batch(vx_ctx* c, int P, const int32_t* offsets, const float* p1, const float* p2,
                               const double* intr4, const vx_essential_options* opt, uint8_t* mask,
                               vx_essential_result* out) {
-    if (!c || P < 0 || (P > 0 && (!offsets || !intr4 || !opt || !out)))
-        return c ? set_error(c, VX_ERR_INVALID, "vx_essential_ransac_batch: bad arguments") : VX_ERR_INVALID;
-    if (P == 0) return VX_OK;
-    if (P > 65535) return set_error(c, VX_ERR_INVALID, "at most 65535 problems per batch");
-    if (offsets[0] != 0) return set_error(c, VX_ERR_INVALID, "offsets[0] must be 0");
-    int hmax = 1;
-    for (int p = 0; p < P; ++p) {
-        if (offsets[p + 1] < offsets[p]) return set_error(c, VX_ERR_INVALID, "offsets must be non-decreasing");
-        if (opt[p].max_iterations > kMaxHyp)
-            return set_error(c, VX_ERR_INVALID, "max_iterations %d > %d", opt[p].max_iterations, kMaxHyp);
+    auto check = [&](int p) {
         if (!(opt[p].threshold >= 0.0)) return set_error(c, VX_ERR_INVALID, "bad threshold (problem %d)", p);
         const double* k = intr4 + 4 * p;
         if (!(k[0] != 0.0 && k[1] != 0.0 && k[0] + k[1] != 0.0))
             return set_error(c, VX_ERR_INVALID, "bad focal length (problem %d)", p);
-        hmax = std::max(hmax, opt[p].max_iterations);
-    }
-    const int64_t N = offsets[P];
-    if (N > 0 && (!p1 || !p2)) return set_error(c, VX_ERR_INVALID, "vx_essential_ransac_batch: null points");
-    if (N > INT32_MAX / 2) return set_error(c, VX_ERR_INVALID, "too many matches");
-    VX_HIP(c, hipSetDevice(c->device));
-    const size_t o_off = 0, o_intr = align16(o_off + (P + 1) * sizeof(int32_t)),
-                 o_opt = align16(o_intr + (size_t)P * 4 * sizeof(double)),
-                 o_p1 = align16(o_opt + (size_t)P * sizeof(vx_essential_options)),
-                 o_p2 = align16(o_p1 + (size_t)N * 2 * sizeof(float)),
-                 in_bytes = align16(o_p2 + (size_t)N * 2 * sizeof(float));
-    VX_HIP(c, c->rs_host.ensure(in_bytes));
-    uint8_t* hs = static_cast<uint8_t*>(c->rs_host.p);
-    std::memcpy(hs + o_off, offsets, (P + 1) * sizeof(int32_t));
-    std::memcpy(hs + o_intr, intr4, (size_t)P * 4 * sizeof(double));
-    std::memcpy(hs + o_opt, opt, (size_t)P * sizeof(vx_essential_options));
-    if (N) {
-        std::memcpy(hs + o_p1, p1, (size_t)N * 2 * sizeof(float));
-        std::memcpy(hs + o_p2, p2, (size_t)N * 2 * sizeof(float));
-    }
-    VX_HIP(c, c->rs_in.ensure(in_bytes));
-    VX_HIP(c, hipMemcpyAsync(c->rs_in.p, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    const size_t out_bytes = align16((size_t)P * sizeof(vx_essential_result)) + (size_t)std::max<int64_t>(N, 1);
-    VX_HIP(c, c->rs_out.ensure(out_bytes));
-    uint8_t* din = c->rs_in.as<uint8_t>();
-    EmDeviceArgs d{};
-    d.offsets = reinterpret_cast<const int*>(din + o_off);
-    d.intr = reinterpret_cast<const double*>(din + o_intr);
-    d.opt = reinterpret_cast<const vx_essential_options*>(din + o_opt);
-    d.p1 = reinterpret_cast<const float*>(din + o_p1);
-    d.p2 = reinterpret_cast<const float*>(din + o_p2);
-    d.out = c->rs_out.as<vx_essential_result>();
-    d.mask = c->rs_out.as<uint8_t>() + align16((size_t)P * sizeof(vx_essential_result));
-    int nmax = 1;
-    for (int p = 0; p < P; ++p) nmax = std::max(nmax, offsets[p + 1] - offsets[p]);
-    int rc;
-    if ((rc = ess_enqueue(c, P, hmax, nmax, d, c->rs_hyp))) return rc;
-    VX_HIP(c, c->rs_host_out.ensure(out_bytes));
-    VX_HIP(c, hipMemcpyAsync(c->rs_host_out.p, c->rs_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-    const uint8_t* ho = static_cast<const uint8_t*>(c->rs_host_out.p);
-    std::memcpy(out, ho, (size_t)P * sizeof(vx_essential_result));
-    if (mask && N) std::memcpy(mask, ho + align16((size_t)P * sizeof(vx_essential_result)), (size_t)N);
-    return VX_OK;
+        return (int)VX_OK;
+    };
+    // one packed upload: offsets | intr | options | p1 | p2 (2 * N floats of either index in an int)
+    return rs::batch_call<EmDeviceArgs>(
+        c, "vx_essential_ransac_batch", P, offsets, intr4, opt, p1, 2, p2, 2, INT32_MAX / 2, "too many matches", mask,
+        out, check, [&](const EmDeviceArgs& d, int hmax) {
+            int nmax = 1;
+            for (int p = 0; p < P; ++p) nmax = std::max(nmax, offsets[p + 1] - offsets[p]);
+            return ess_enqueue(c, P, hmax, nmax, d, c->rs_hyp);
+        });
 }
 
 int vx_essential_ransac(vx_ctx* c, const float* p1, const float* p2, int n, const double* intr4,

@@ -36,8 +36,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxWg = 512;
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct CaptureArgs {
     const uint8_t* src_kp;    // the slot's vx_keypoint rows
     const uint8_t* src_desc;  // its descriptor rows

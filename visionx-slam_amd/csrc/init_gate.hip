@@ -218,8 +218,6 @@ __global__ void __launch_bounds__(kBlock) k_init_gate(GateArgs a) {
     r->stddev = stddev;
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int check_args(vx_ctx* c, const void* img, int w, int h, int ch, int64_t stride, int64_t xy_stride,
                const vx_init_gate_options* opt) {
     if (!img || !opt) return set_error(c, VX_ERR_INVALID, "vx_init_gate: null image / options");

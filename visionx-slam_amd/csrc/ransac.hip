@@ -6,9 +6,10 @@
 // budget, repeats.  Here every hypothesis of the budget is drawn, solved and scored at once — one
 // workgroup per (hypothesis, problem), the scoring pass reading the problem's correspondences
 // (20 B each) from L2 — and the sequential loop is then replayed over the per-hypothesis inlier
-// counts in hypothesis order (one thread, <= 4096 steps of integer compares and the
-// RANSACUpdateNumIters formula), so the kept model and the reported iteration count are exactly
-// those of a sequential run over the same hypothesis stream.  The kept model's inliers are then
+// counts in hypothesis order (rs::replay, ransac_common.hpp: one wave, 64 hypotheses at a time,
+// integer compares and the RANSACUpdateNumIters formula), so the kept model and the reported
+// iteration count are exactly those of a sequential run over the same hypothesis stream.  The kept
+// model's inliers are then
 // refined by Levenberg-Marquardt in one workgroup (solvePnPRansac's SOLVEPNP_ITERATIVE refit).
 //
 //   k_pnp_hyp     grid (H, problems)  sample 4 (splitmix64 counter stream), P3P (Grunert quartic,
@@ -19,13 +20,7 @@
 // The hypothesis stage uses only + - * / and sqrt in a fixed order (-ffp-contract=off), so its
 // models, counts, the kept hypothesis and the mask are bit-identical to the CPU restatement
 // (oracle/ransac_oracle.cpp, the specification); the LM refit matches it to rounding.
-#include <algorithm>
-#include <cfloat>
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "vx_internal.hpp"
+#include "ransac_common.hpp"
 #include "ba_common.hpp"
 
 namespace vx {
@@ -34,7 +29,6 @@ namespace {
 using namespace vx::ba;
 
 constexpr int kThreads = 256;
-constexpr int kMaxHyp = 4096;
 
 struct HypRec {
     double R[9], t[3];
@@ -42,23 +36,10 @@ struct HypRec {
 };
 
 struct PnpArgs {
-    const int* offsets;           // P + 1
-    const double* intr;           // 4 per problem
-    const vx_pnp_options* opt;    // per problem
-    const float* obj;             // 3 per correspondence
-    const float* img;             // 2 per correspondence
-    HypRec* hyp;                  // [P][hmax]
+    PnpDeviceArgs d;
+    HypRec* hyp;  // [P][hmax]
     int hmax;
-    vx_pnp_result* out;           // per problem
-    uint8_t* mask;                // per correspondence
 };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 // ---------------------------------------------------------------- real polynomial roots (d <= 4)
 // Degrees are template parameters and every small array is indexed by unrolled compile-time
@@ -334,22 +315,11 @@ __device__ __forceinline__ D3 bearing(const float* img, int i, const double* cam
 // hypothesis h of a problem with n correspondences: sample 4 distinct, P3P, 4th-point choice
 __device__ bool hypothesis(const float* obj, const float* img, int n, const double* cam, uint64_t seed, int h,
                            Model* best) {
-    int i0 = -1, i1 = -1, i2 = -1, i3 = -1;
-    int got = 0;
-    for (int a = 0; a < 64 && got < 4; ++a) {
-        const uint64_t x = mix64(seed + (uint64_t)h * 64u + (uint64_t)a);
-        const int i = (int)(((x >> 32) * (uint64_t)n) >> 32);
-        if (i == i0 || i == i1 || i == i2) continue;
-        if (got == 0) i0 = i;
-        else if (got == 1) i1 = i;
-        else if (got == 2) i2 = i;
-        else i3 = i;
-        ++got;
-    }
-    if (got < 4) return false;
-    const D3 P[3] = {world_pt(obj, i0), world_pt(obj, i1), world_pt(obj, i2)};
-    const D3 f[3] = {bearing(img, i0, cam), bearing(img, i1, cam), bearing(img, i2, cam)};
-    return p3p_best(P, f, world_pt(obj, i3), (double)img[2 * i3], (double)img[2 * i3 + 1], cam, best);
+    int i[4];
+    if (!rs::draw_distinct(seed, h, n, i)) return false;
+    const D3 P[3] = {world_pt(obj, i[0]), world_pt(obj, i[1]), world_pt(obj, i[2])};
+    const D3 f[3] = {bearing(img, i[0], cam), bearing(img, i[1], cam), bearing(img, i[2], cam)};
+    return p3p_best(P, f, world_pt(obj, i[3]), (double)img[2 * i[3]], (double)img[2 * i[3] + 1], cam, best);
 }
 
 __device__ __forceinline__ bool is_inlier(const double* R, const double* t, const float* obj, const float* img, int i,
@@ -358,21 +328,14 @@ __device__ __forceinline__ bool is_inlier(const double* R, const double* t, cons
     return reproj_sq(R, t, world_pt(obj, i), (double)img[2 * i], (double)img[2 * i + 1], cam, &e) && e <= thr2;
 }
 
-// block-wide integer sum of per-thread flags (ballot + popcount per wave, LDS atomics)
-__device__ __forceinline__ void block_count(int flag, int* lds_cnt) {
-    const uint64_t b = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) atomicAdd(lds_cnt, __popcll(b));
-}
-
 __global__ void __launch_bounds__(kThreads) k_pnp_hyp(PnpArgs a) {
     const int p = blockIdx.y, h = blockIdx.x;
-    const vx_pnp_options o = a.opt[p];
-    const int H = min(min(max(o.max_iterations, 0), kMaxHyp), a.hmax);  // (hmax: grid x and record stride)
-    if (h >= H) return;
-    const int b = a.offsets[p], n = a.offsets[p + 1] - b;
-    const float* obj = a.obj + 3 * (size_t)b;
-    const float* img = a.img + 2 * (size_t)b;
-    double cam[4] = {a.intr[4 * p], a.intr[4 * p + 1], a.intr[4 * p + 2], a.intr[4 * p + 3]};
+    const vx_pnp_options o = a.d.opt[p];
+    if (h >= rs::hyp_budget(o.max_iterations, a.hmax)) return;
+    const int b = a.d.offsets[p], n = a.d.offsets[p + 1] - b;
+    const float* obj = a.d.obj + 3 * (size_t)b;
+    const float* img = a.d.img + 2 * (size_t)b;
+    double cam[4] = {a.d.intr[4 * p], a.d.intr[4 * p + 1], a.d.intr[4 * p + 2], a.d.intr[4 * p + 3]};
     __shared__ double sR[9], st[3];
     __shared__ int svalid, scnt;
     if (threadIdx.x == 0) {
@@ -400,7 +363,7 @@ __global__ void __launch_bounds__(kThreads) k_pnp_hyp(PnpArgs a) {
     const double thr2 = o.reproj_error * o.reproj_error;
     for (int i0 = 0; i0 < n; i0 += kThreads) {
         const int i = i0 + threadIdx.x;
-        block_count(i < n && is_inlier(R, t, obj, img, i, cam, thr2), &scnt);
+        rs::block_count(i < n && is_inlier(R, t, obj, img, i, cam, thr2), &scnt);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -409,21 +372,6 @@ __global__ void __launch_bounds__(kThreads) k_pnp_hyp(PnpArgs a) {
         rec->valid = 1;
         rec->count = scnt;
     }
-}
-
-// RANSACUpdateNumIters for modelPoints = 4
-__device__ int update_num_iters(double p, double ep, int max_iters) {
-    p = fmax(p, 0.0);
-    p = fmin(p, 1.0);
-    ep = fmax(ep, 0.0);
-    ep = fmin(ep, 1.0);
-    double num = fmax(1.0 - p, DBL_MIN);
-    const double x = 1.0 - ep;
-    double denom = 1.0 - (x * x) * (x * x);
-    if (denom < DBL_MIN) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0.0 || -num >= (double)max_iters * -denom ? max_iters : (int)rint(num / denom);
 }
 
 __device__ void quat_of(const double* R, double* q) {
@@ -503,69 +451,37 @@ __device__ void accumulate(const double* T, const float* obj, const float* img, 
     }
 }
 
-// RANSACPointSetRegistrator::run's loop replayed by wave 0 over the hypothesis records, 64 at a
-// time: a hypothesis can only be kept if its count beats every earlier count and 3 (an in-wave
-// prefix max + ballot finds those "records"); the records are then walked in order, each shrinking
-// the iteration budget, until one lies beyond the budget.  Returns {kept, hypotheses run, count}.
-__device__ int3 replay(const HypRec* rec, int H, int n, double confidence) {
-    const int lane = threadIdx.x & 63;
-    int niters = n >= 4 ? H : 0, best = -1, good = 0;
-    for (int base = 0; base < niters; base += 64) {
-        const int h = base + lane;
-        const int c = (h < niters && rec[h].valid) ? rec[h].count : -1;
-        int incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(incl, off);
-            if (lane >= off) incl = max(incl, y);
-        }
-        int excl = __shfl_up(incl, 1);
-        if (lane == 0) excl = -1;
-        uint64_t m = __ballot(c > max(max(excl, good), 3));
-        bool stop = false;
-        while (m) {
-            const int k = __ffsll((unsigned long long)m) - 1;
-            const int hk = base + k;
-            if (hk >= niters) {
-                stop = true;
-                break;
-            }
-            const int ck = __shfl(c, k);
-            best = hk;
-            good = ck;
-            niters = update_num_iters(confidence, (double)(n - ck) / (double)n, niters);
-            m &= m - 1;
-        }
-        if (stop) break;
-    }
-    return make_int3(best, best >= 0 ? max(niters, best + 1) : niters, good);
-}
-
 __global__ void __launch_bounds__(kRefineThreads) k_pnp_refine(PnpArgs a) {
     const int p = blockIdx.x;
-    const vx_pnp_options o = a.opt[p];
-    const int H = min(min(max(o.max_iterations, 0), kMaxHyp), a.hmax);  // (hmax: grid x and record stride)
-    const int b = a.offsets[p], n = a.offsets[p + 1] - b;
-    const float* obj = a.obj + 3 * (size_t)b;
-    const float* img = a.img + 2 * (size_t)b;
-    uint8_t* mask = a.mask + b;
-    const double cam[4] = {a.intr[4 * p], a.intr[4 * p + 1], a.intr[4 * p + 2], a.intr[4 * p + 3]};
+    const vx_pnp_options o = a.d.opt[p];
+    const int H = rs::hyp_budget(o.max_iterations, a.hmax);
+    const int b = a.d.offsets[p], n = a.d.offsets[p + 1] - b;
+    const float* obj = a.d.obj + 3 * (size_t)b;
+    const float* img = a.d.img + 2 * (size_t)b;
+    uint8_t* mask = a.d.mask + b;
+    const double cam[4] = {a.d.intr[4 * p], a.d.intr[4 * p + 1], a.d.intr[4 * p + 2], a.d.intr[4 * p + 3]};
     const HypRec* rec = a.hyp + (size_t)p * a.hmax;
     // sfin (step finite, set before the trial pass) and sgo (continue, set after it) are separate
     // so a thread still reading one iteration's flag never sees thread 0's next write
     __shared__ int sbest, srun, sgood, sfin, sgo;
     __shared__ double sT[7], sT1[7], sacc[kAcc], lds[(kRefineThreads / 64) * kAcc], red[kAcc];
     if (threadIdx.x < 64) {
-        const int3 r = replay(rec, H, n, o.confidence);
+        // the loop replay (wave 0), one model per hypothesis; k_pnp_hyp writes both fields of every record
+        // below H, and both are loaded before either is used: one memory round trip per block, not two
+        auto count_at = [rec](int h, int) {
+            const int valid = rec[h].valid, count = rec[h].count;
+            return valid ? count : -1;
+        };
+        const int4 r = rs::replay<1, 4>(count_at, H, n, o.confidence);
         if (threadIdx.x == 0) {
             sbest = r.x;
-            srun = r.y;
-            sgood = r.z;
+            srun = r.z;
+            sgood = r.w;
         }
     }
     __syncthreads();
     const int best = sbest;
-    vx_pnp_result* r = a.out + p;
+    vx_pnp_result* r = a.d.out + p;
     if (best < 0) {
         for (int i = threadIdx.x; i < n; i += kRefineThreads) mask[i] = 0;
         if (threadIdx.x == 0) {
@@ -666,22 +582,11 @@ __global__ void __launch_bounds__(kRefineThreads) k_pnp_refine(PnpArgs a) {
     }
 }
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
 int pnp_enqueue(vx_ctx* c, int P, int hmax, const PnpDeviceArgs& d, DevBuf& hyp) {
     VX_HIP(c, hyp.ensure((size_t)P * hmax * sizeof(HypRec)));
-    PnpArgs a{};
-    a.offsets = d.offsets;
-    a.intr = d.intr;
-    a.opt = d.opt;
-    a.obj = d.obj;
-    a.img = d.img;
-    a.hyp = hyp.as<HypRec>();
-    a.hmax = hmax;
-    a.out = d.out;
-    a.mask = d.mask;
+    const PnpArgs a{d, hyp.as<HypRec>(), hmax};
     VX_HIP(c, launch(c, kStPnpHyp, k_pnp_hyp, dim3(hmax, P), dim3(kThreads), 0, c->stream, a));
     VX_HIP(c, launch(c, kStPnpRefine, k_pnp_refine, dim3(P), dim3(kRefineThreads), 0, c->stream, a));
     return VX_OK;
@@ -704,62 +609,18 @@ void vx_pnp_default_options(int n_points, vx_pnp_options* o) {
 
 int vx_pnp_ransac_batch(vx_ctx* c, int P, const int32_t* offsets, const float* obj, const float* img,
                         const double* intr4, const vx_pnp_options* opt, uint8_t* inlier_mask, vx_pnp_result* out) {
-    if (!c || P < 0 || (P > 0 && (!offsets || !intr4 || !opt || !out)))
-        return c ? set_error(c, VX_ERR_INVALID, "vx_pnp_ransac_batch: bad arguments") : VX_ERR_INVALID;
-    if (P == 0) return VX_OK;
-    if (P > 65535) return set_error(c, VX_ERR_INVALID, "at most 65535 problems per batch");
-    if (offsets[0] != 0) return set_error(c, VX_ERR_INVALID, "offsets[0] must be 0");
-    int hmax = 1;
-    for (int p = 0; p < P; ++p) {
-        if (offsets[p + 1] < offsets[p]) return set_error(c, VX_ERR_INVALID, "offsets must be non-decreasing");
-        if (opt[p].max_iterations > kMaxHyp)
-            return set_error(c, VX_ERR_INVALID, "max_iterations %d > %d", opt[p].max_iterations, kMaxHyp);
+    auto check = [&](int p) {
         if (opt[p].refine_iterations < 0 || !(opt[p].reproj_error >= 0.0))
             return set_error(c, VX_ERR_INVALID, "bad options for problem %d", p);
         const double* k = intr4 + 4 * p;
         if (!(k[0] != 0.0 && k[1] != 0.0)) return set_error(c, VX_ERR_INVALID, "zero focal length (problem %d)", p);
-        hmax = std::max(hmax, opt[p].max_iterations);
-    }
-    const int64_t N = offsets[P];
-    if (N > 0 && (!obj || !img)) return set_error(c, VX_ERR_INVALID, "vx_pnp_ransac_batch: null points");
-    if (N > INT32_MAX / 3) return set_error(c, VX_ERR_INVALID, "too many correspondences");
-    VX_HIP(c, hipSetDevice(c->device));
-    // one packed upload: offsets | intr | options | obj | img
-    const size_t o_off = 0, o_intr = align16(o_off + (P + 1) * sizeof(int32_t)),
-                 o_opt = align16(o_intr + (size_t)P * 4 * sizeof(double)),
-                 o_obj = align16(o_opt + (size_t)P * sizeof(vx_pnp_options)),
-                 o_img = align16(o_obj + (size_t)N * 3 * sizeof(float)),
-                 in_bytes = align16(o_img + (size_t)N * 2 * sizeof(float));
-    VX_HIP(c, c->rs_host.ensure(in_bytes));
-    uint8_t* hs = static_cast<uint8_t*>(c->rs_host.p);
-    std::memcpy(hs + o_off, offsets, (P + 1) * sizeof(int32_t));
-    std::memcpy(hs + o_intr, intr4, (size_t)P * 4 * sizeof(double));
-    std::memcpy(hs + o_opt, opt, (size_t)P * sizeof(vx_pnp_options));
-    if (N) {
-        std::memcpy(hs + o_obj, obj, (size_t)N * 3 * sizeof(float));
-        std::memcpy(hs + o_img, img, (size_t)N * 2 * sizeof(float));
-    }
-    VX_HIP(c, c->rs_in.ensure(in_bytes));
-    VX_HIP(c, hipMemcpyAsync(c->rs_in.p, hs, in_bytes, hipMemcpyHostToDevice, c->stream));
-    const size_t out_bytes = align16((size_t)P * sizeof(vx_pnp_result)) + (size_t)std::max<int64_t>(N, 1);
-    VX_HIP(c, c->rs_out.ensure(out_bytes));
-    uint8_t* din = c->rs_in.as<uint8_t>();
-    PnpDeviceArgs a{};
-    a.offsets = reinterpret_cast<const int*>(din + o_off);
-    a.intr = reinterpret_cast<const double*>(din + o_intr);
-    a.opt = reinterpret_cast<const vx_pnp_options*>(din + o_opt);
-    a.obj = reinterpret_cast<const float*>(din + o_obj);
-    a.img = reinterpret_cast<const float*>(din + o_img);
-    a.out = c->rs_out.as<vx_pnp_result>();
-    a.mask = c->rs_out.as<uint8_t>() + align16((size_t)P * sizeof(vx_pnp_result));
-    if (int rc = pnp_enqueue(c, P, hmax, a, c->rs_hyp)) return rc;
-    VX_HIP(c, c->rs_host_out.ensure(out_bytes));
-    VX_HIP(c, hipMemcpyAsync(c->rs_host_out.p, c->rs_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-    const uint8_t* ho = static_cast<const uint8_t*>(c->rs_host_out.p);
-    std::memcpy(out, ho, (size_t)P * sizeof(vx_pnp_result));
-    if (inlier_mask && N) std::memcpy(inlier_mask, ho + align16((size_t)P * sizeof(vx_pnp_result)), (size_t)N);
-    return VX_OK;
+        return (int)VX_OK;
+    };
+    // one packed upload: offsets | intr | options | obj | img (3 * N floats of obj index in an int)
+    return rs::batch_call<PnpDeviceArgs>(
+        c, "vx_pnp_ransac_batch", P, offsets, intr4, opt, obj, 3, img, 2, INT32_MAX / 3, "too many correspondences",
+        inlier_mask, out, check,
+        [&](const PnpDeviceArgs& d, int hmax) { return pnp_enqueue(c, P, hmax, d, c->rs_hyp); });
 }
 
 int vx_pnp_ransac(vx_ctx* c, const float* obj, const float* img, int n, const double* intr4,

@@ -14,7 +14,6 @@ constexpr int kWaves = kBlock / 64;
 
 // The packed result block of vx_track_pnp_async / vx_track_essential_async (R = its record):
 // R | pair_match[cap] | mask[cap], each part on a 16-byte boundary.
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 template <class R>
 __host__ __device__ inline size_t off_pair_match() { return align16(sizeof(R)); }
 template <class R>

@@ -132,6 +132,7 @@ struct PinnedBuf {
 };
 
 inline size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }  // (kernels use it too)
 
 // A host block staged in pinned memory and uploaded into a device block of its own in one copy, the
 // staging guarded by an event: begin() waits until the previous upload has left the staging (the one
