@@ -211,7 +211,14 @@ __device__ __forceinline__ void sym3_inv(const double* m, double* out) {
 // blocks: H = [A B; B^T C], W = A^-1 B, S = C - B^T W, x2 = S^-1 (b2 - B^T A^-1 b1), x1 = A^-1 b1 -
 // W x2.  Same solution as an LDLT up to rounding, with a dependent chain of ~35 FP64 ops instead
 // of ~100 (the one-thread-per-keyframe pose solve of k_landmark_solve sits on the LocalBA
-// critical path).  A singular block gives a non-finite x, which the caller rejects.
+// critical path).  The explicit inverses are not backward stable: they lose what the two determinants
+// and the Schur complement cancel, a relative error of about eps / (hA hS cS) with hA = det A /
+// (a00 a11 a22), hS the same of S and cS = min s_ii / c_ii, where an LDL^T loses eps * kappa(H).  A
+// keyframe with dozens of spread observations has hA hS cS ~ 0.1; one whose J^T J lacks ONE rank
+// (collinear points: kappa 2e8 under the damping) 1e-8 ~ 1 / kappa, still within what an LDL^T gives;
+// one with fewer than three observations lacks two ranks or more (rank J^T J <= 2 obs), both
+// determinants cancel, hA hS cS ~ 1e-18 under kappa 1e12 and x is noise: those go to
+// ldlt6_packed_solve (ba.hip solve_pose<true>; tests/test_gpu_ba_step.py).
 __device__ __forceinline__ void spd6_block_solve(const double* U, const double* b, double* x) {
     const double A[6] = {U[0], U[1], U[2], U[6], U[7], U[11]};  // (00 01 02 11 12 22)
     const double B[3][3] = {{U[3], U[4], U[5]}, {U[8], U[9], U[10]}, {U[12], U[13], U[14]}};
@@ -247,6 +254,42 @@ __device__ __forceinline__ void spd6_block_solve(const double* U, const double* 
 // upper-triangle index of the 6x6 pose Hessian
 __device__ __forceinline__ int hidx(int i, int j) {  // i <= j
     return i * 6 - (i * (i - 1)) / 2 + (j - i);
+}
+
+// x = H^-1 b by an unpivoted LDL^T in place on the packed upper triangle U (hidx layout; destroyed):
+// the backward-stable solve for the rare system spd6_block_solve cannot take.  Right-looking, so
+// nothing lives beside U, b and one column, where ldlt_spd_solve<6> keeps a full L and its tree-sum
+// operands beside A; the chain is longer, which the rare path can afford.  Zero pivots as in
+// ldlt_spd_solve.
+__device__ __forceinline__ void ldlt6_packed_solve(double* U, const double* b, double* x) {
+    double inv[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double d = U[hidx(k, k)];
+        const double ik = fabs(d) > 0.0 ? frcp(d) : 1.0;
+        inv[k] = fabs(d) > 2.2250738585072014e-308 ? frcp(d) : 0.0;
+        double l[6];
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) l[i] = U[hidx(k, i)] * ik;
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) U[hidx(i, j)] -= l[i] * U[hidx(k, j)];
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) U[hidx(k, i)] = l[i];  // L(i, k)
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = b[i];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) x[i] -= U[hidx(k, i)] * x[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] *= inv[i];
+#pragma unroll
+    for (int k = 4; k >= 0; --k)
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) x[k] -= U[hidx(k, i)] * x[i];
 }
 
 // Sophus SE3::exp(dx) * T, written into T (8 doubles)
