@@ -112,6 +112,41 @@ def test_shard_emulation_rejects_mismatched_plans(ctx):
     a.close(), b.close(), c.close()
 
 
+@pytest.mark.parametrize("env, fused, persistent", [
+    ({"VX_BA_ATOMIC_ROWS": "0", "VX_BA_PERSIST": "1"}, 1, False),   # k_ba_iter, rows by partial slots
+    ({"VX_BA_ATOMIC_ROWS": "0", "VX_BA_PERSIST": "0"}, 1, False),
+    ({"VX_BA_ATOMIC_ROWS": "0", "VX_BA_FUSED": "0"}, 0, False),     # k_pose_kf + k_landmark_solve
+    ({"VX_BA_PERSIST": "1"}, 1, True),                              # k_ba_win (its rows: tagged slots, in slot order)
+], ids=["slots-persist1", "slots-persist0", "two-kernel", "window"])
+def test_one_unsharded_plan_through_the_emulation_is_the_real_run(ctx, monkeypatch, env, fused, persistent):
+    """vx_ba_shard_emulate_run over ONE unsharded plan has nothing to reduce over shards: it is the run
+    vx_ba_plan_run_async makes (csrc/ba.hip run_window, n = 1) — the same kernels, so the same pose and
+    landmark bytes and the same stats as a second plan of the window run the usual way.  Every form here
+    sums its rows in a fixed order, so two runs agree bitwise."""
+    for k in ("VX_BA_ATOMIC_ROWS", "VX_BA_PERSIST", "VX_BA_FUSED", "VX_BA_PEER"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    m = synth.make_ba_map(7, 12, 2000, n_old_kf=2)
+    opts = vxslam.default_ba_options(window=12)
+    p, q = ctx.ba_plan(m, opts), ctx.ba_plan(m, opts)
+    try:
+        for plan in (p, q):  # (the environment is read at plan build)
+            assert plan.layout()["fused"] == fused and plan.persistent() == persistent
+        ctx.ba_shard_emulate([p])
+        q.run_async()
+        got, want = m.copy(), m.copy()
+        sg, sw = p.fetch(got), q.fetch(want)
+        assert sw.iterations >= 1 and sw.obs[0] > 0  # (the window optimises something)
+        assert (sg.status, sg.iterations, list(sg.obs[:16]), list(sg.cost[:16])) == \
+               (sw.status, sw.iterations, list(sw.obs[:16]), list(sw.cost[:16]))
+        assert got["kf_pose"].tobytes() == want["kf_pose"].tobytes()
+        assert got["lm_pos"].tobytes() == want["lm_pos"].tobytes()
+        assert not np.array_equal(want["lm_pos"], m["lm_pos"])
+    finally:
+        p.close(), q.close()
+
+
 def test_landmark_with_more_observations_than_a_workgroup(ctx, oracle):
     """A snapshot that lists a landmark's (keyframe, feature) pairs over and over (600+ entries,
     more than the 512 observations of a k_landmark_solve workgroup; a Landmark's unordered_map

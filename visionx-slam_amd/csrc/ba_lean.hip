@@ -42,6 +42,7 @@
 // identical iteration and observation counts (tests/test_gpu_dmap.py).
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -815,42 +816,43 @@ int lean_optimize(vx_ctx* c, vx_dmap* m, uint64_t ref, int has_ref, const vx_ba_
     hipStream_t sm = c->stream;
     VX_HIP(c, grow(L.kf_pose, ((size_t)nk + 1) * 128));
     VX_HIP(c, grow(L.kf_rot, ((size_t)nk + 1) * 72));
-    VX_HIP(c, grow(L.kf_part, ((size_t)nk + 1) * n_split * kBaStrideDoubles * 8));
+    VX_HIP(c, grow(L.kf_part, ((size_t)nk + 1) * n_split * kBaStride * 8));
     VX_HIP(c, grow(L.kf_cost, ((size_t)nk + 1) * 16));
-    VX_HIP(c, grow(L.state, ba_state_bytes()));
+    VX_HIP(c, grow(L.state, sizeof(BAState)));
     VX_HIP(c, grow(L.lm_pos, ((size_t)nl + 1) * 32));
 
     DynPlan d;
-    d.n_kf = nk;
-    d.n_split = n_split;
     d.grid_blocks = cap_blocks;
-    d.opt = o;
-    d.kf_pose0 = a.kf_pose0;
-    d.kf_pose = L.kf_pose.as<double>();
-    d.kf_intr = a.kf_intr;
-    d.kf_rot = L.kf_rot.as<double>();
-    d.kf_flags = a.kf_flags;
-    d.kf_obs_ptr = a.kf_obs_ptr;
-    d.kf_part = L.kf_part.as<double>();
-    d.kf_cost = L.kf_cost.as<double>();
-    d.lm_pos0 = a.lm_pos0;
-    d.lm_pos = L.lm_pos.as<double>();
-    d.pobs_uv = a.puv;
-    d.pobs_lm = a.plm;
-    d.lobs_ptr = a.lobs_ptr;
-    d.lobs_kf = a.lkf;
-    d.lobs_lm = a.llm;
-    d.lm_blk = a.lm_blk;
-    d.lobs_uv = a.luv;
-    d.state = L.state.p;
-    d.dyn = a.dyn;
+    BAArgs& r = d.a;  // (n_opt, n_lm: from dyn, on the device)
+    r.n_kf = nk;
+    r.n_split = n_split;
+    ba_set_options(r, o);
+    r.kf_pose0 = a.kf_pose0;
+    r.kf_pose = L.kf_pose.as<double>();
+    r.kf_intr = a.kf_intr;
+    r.kf_rot = L.kf_rot.as<double>();
+    r.kf_flags = a.kf_flags;
+    r.kf_obs_ptr = a.kf_obs_ptr;
+    r.kf_part = L.kf_part.as<double>();
+    r.kf_cost = L.kf_cost.as<double>();
+    r.lm_pos0 = a.lm_pos0;
+    r.lm_pos = L.lm_pos.as<double>();
+    r.pobs_uv = a.puv;
+    r.pobs_lm = a.plm;
+    r.lobs_ptr = a.lobs_ptr;
+    r.lobs_kf = a.lkf;
+    r.lobs_lm = a.llm;
+    r.lm_blk = a.lm_blk;
+    r.lobs_uv = a.luv;
+    r.state = L.state.as<BAState>();
+    r.dyn = a.dyn;
     if (o.max_iterations > 0) {
         if ((rc = ba_run_dyn(c, d))) return rc;
     }
     // the end: the header (and the iteration state) back — the call's only synchronisation; with
     // vx_dmap_prefetch_results the results too (both pose parities, positions and rows by capacity).
     // After a run, k_lb_apply packs all of it into one device block and ONE copy brings it back.
-    const size_t sb = ba_state_bytes();
+    const size_t sb = sizeof(BAState);
     const size_t hdr_b = kDynInts * 4 + sb, hdr_pad = (hdr_b + 63) & ~(size_t)63;
     const bool pf = L.prefetch && o.max_iterations > 0;
     const size_t pose_b = 2 * (size_t)nk * 64, pos_b = (size_t)nl * 32, rows_b = (size_t)nl * 4;
@@ -859,7 +861,7 @@ int lean_optimize(vx_ctx* c, vx_dmap* m, uint64_t ref, int has_ref, const vx_ba_
     if (o.max_iterations > 0) {
         VX_HIP(c, grow(L.pack, pack_b));
         // (the apply takes the last iteration's pose buffer from BAState::iterations on the device)
-        const int* iters = reinterpret_cast<const int*>(static_cast<const uint8_t*>(L.state.p) + ba_state_iter_offset());
+        const int* iters = reinterpret_cast<const int*>(static_cast<const uint8_t*>(L.state.p) + offsetof(BAState, iterations));
         hipLaunchKernelGGL(k_lb_apply, dim3(grid(std::max<long long>(std::max<long long>(nk, nl), (long long)hdr_b / 4))),
                            dim3(kT), 0, sm, (const int*)a.dyn, iters, nk, a.win, (const double*)L.kf_pose.as<double>(),
                            (const int*)a.inv, nl, (const double*)L.lm_pos.as<double>(), m->kf_pose.as<double>(),
@@ -884,7 +886,11 @@ int lean_optimize(vx_ctx* c, vx_dmap* m, uint64_t ref, int has_ref, const vx_ba_
     s.status = H[kDynStatus];
     s.n_landmarks = H[kDynGlobal];
     // (with no optimisable landmark no kernel of the run touched the state: iterations stay 0)
-    if (s.status == 0 && o.max_iterations > 0) ba_state_to_stats(H + kDynInts, &s);
+    if (s.status == 0 && o.max_iterations > 0) {
+        BAState hs;
+        std::memcpy(&hs, H + kDynInts, sb);
+        state_to_stats(hs, &s);
+    }
     L.nk = nk;
     L.status = s.status;
     L.n_opt = H[kDynNOpt];

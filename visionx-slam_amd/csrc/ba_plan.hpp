@@ -1,5 +1,8 @@
-// ba_plan.hpp — the LocalBA plan (vx_ba_plan) shared by its two builders: the host reference
-// build (ba.hip, build_plan) and the device build (ba_window.hip, build_plan_device).
+// ba_plan.hpp — what the LocalBA translation units share (ba.hip, ba_window.hip, ba_fused_build.hip,
+// ba_lean.hip): the plan (vx_ba_plan) and its two builders' entry points (ba.hip build_plan, ba_window.hip
+// build_plan_device), the fused layout's constants, and the records every run hands to the kernels — the
+// iteration state BAState and the argument record BAArgs with the one filler of its options half, so a
+// caller outside ba.hip (the lean plan of ba_lean.hip) fills a BAArgs itself.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -25,7 +28,7 @@ struct vx_ba_plan {
         pobs_uv, pobs_lm, lobs_ptr, lobs_kf, lobs_lm, lm_blk, lobs_uv, state;
     int n_lm_blocks = 1;
     int max_lm_obs = 0;         // most landmark-stage observations of one landmark
-    bool choice_made = false;   // kernel set decided (ba.hip choose_lds_poses; sharded: over all ranks)
+    bool choice_made = false;   // kernel set decided (ba.hip choose_kernels: over every shard of the window)
     bool lds_poses = true;
     bool ran = false;
     vx::OwnedGraph graph;  // the run's launch sequence, replayed by hipGraphLaunch
@@ -38,7 +41,7 @@ struct vx_ba_plan {
     // and the pose-stage observations of its landmarks grouped by keyframe; per-keyframe partial
     // slots (n_kf x f_maxl x 32 doubles) summed in slot order by every workgroup that needs the pose
     bool fused = false;
-    bool fused_all = false;  // sharded: every rank has a fused layout (decided at the first run)
+    bool fused_all = false;  // every shard of the window has a fused layout (choose_kernels): the fused form runs
     int f_blocks = 0, f_maxl = 0, f_threads = 512;
     vx::DevBuf f_tab, f_lobs_uv, f_pobs_uv, f_pobs_p, f_part;  // f_tab: the index tables, one upload
     vx::DevBuf f_rowpart;                                         // sharded: all-reduced per-row partials
@@ -48,7 +51,7 @@ struct vx_ba_plan {
     bool f_atomic = false;
     // persistent window (k_ba_win, one launch per run): the rows' tagged partial slots per
     // iteration, the owners' stop-rule terms, the workgroups' hello words, the generation word
-    // (ba.hip WinArgs); win_off after a run whose wait ran out
+    // (ba_win_kernel.hpp WinArgs); win_off after a run whose wait ran out (ba.hip win_fallback)
     vx::DevBuf f_win;
     bool f_persist = false, win_off = false;
     size_t win_part_off = 0, win_stop_off = 0, win_hello_off = 0, win_gen_off = 0;
@@ -88,7 +91,7 @@ vx_ba_plan* plan_new(vx_ctx* c);
 #ifndef VX_BA_MAX_SPLIT
 #define VX_BA_MAX_SPLIT 4
 #endif
-constexpr int kBaPoseBlock = VX_BA_POSE_BLOCK;  // k_pose_kf threads per workgroup (ba.hip kPoseBlock)
+constexpr int kBaPoseBlock = VX_BA_POSE_BLOCK;  // k_pose_kf threads per workgroup (ba_kernels.hpp kPoseBlock)
 constexpr int kBaLmBlock = 512;    // k_landmark_solve observations / landmarks per workgroup
 constexpr int kBaMaxSplit = VX_BA_MAX_SPLIT;     // pose-stage workgroups per keyframe
 
@@ -177,33 +180,74 @@ enum : int { kDynNOpt = 0, kDynNLm, kDynBlocks, kDynStatus, kDynPoseObs, kDynLmO
              // observations, co-observation pairs, most observations of one landmark, blocks of the
              // reduced system, k_sba_lm workgroups
              kDynSbaOo, kDynSbaPairs, kDynSbaMaxObs, kDynSbaBlocks, kDynSbaLmBlocks, kDynInts = 16 };
+constexpr int kBaMaxIter = 64;     // most iterations of a run (vx_ba_options::max_iterations)
+
+// the iteration state of a run, on the device (vx_ba_plan::state; a lean plan's state block)
+struct BAState {
+    int active[kBaMaxIter + 1];  // active[it]: iteration it runs
+    int iterations;
+    int fault;                 // k_ba_win: a bounded wait ran out (the run is void; fetch re-runs it)
+    double last_cost;
+    double cost[16];
+    int obs[16];
+};
+
+// the argument record of every LocalBA kernel
+struct BAArgs {
+    int n_kf, n_opt, n_lm, pad0;
+    int min_pose_obs, min_point_obs, max_iter, n_split;
+    double huber, max_err;
+    double huber2, max_err2;     // squared thresholds (gates on |e|^2)
+    const double* kf_pose0;  // 8 per KF: qx qy qz qw tx ty tz 0
+    double* kf_pose;         // 2 x n_kf x 8: ping-pong by iteration parity (see pose_in / pose_out)
+    const double* kf_intr;   // 4 per KF
+    double* kf_rot;          // 9 per KF (rotation matrix of the current pose)
+    const int* kf_flags;     // bit0: keyframe has a camera
+    const int* kf_obs_ptr;   // n_kf + 1, CSR into the pose observations
+    double* kf_part;         // n_kf * n_split * kBaStride partial normal-equation blocks (all-reduced when sharded)
+    double* kf_cost;         // 2 per KF: pose-stage cost and observation count
+    const double* lm_pos0;   // 4 per landmark
+    double* lm_pos;
+    const double2* pobs_uv;
+    const int* pobs_lm;
+    const int* lobs_ptr;     // n_opt + 1
+    const int* lobs_kf;
+    const int* lobs_lm;      // landmark slot of each landmark-stage observation
+    const int* lm_blk;       // k_landmark_solve workgroup -> {first landmark, first observation} (n_blocks + 1)
+    const double2* lobs_uv;
+    BAState* state;
+    // resident one-call build (ba_lean.hip): counts known only on the device — {n_opt, n_lm, landmark
+    // workgroups, status (1: no optimisable landmark, nothing runs), ...}; null for built plans
+    const int* dyn;
+};
+
+// the options half of the record (both fillers: ba.hip make_args, ba_lean.hip lean_optimize)
+inline void ba_set_options(BAArgs& a, const vx_ba_options& o) {
+    a.min_pose_obs = o.min_pose_observations;
+    a.min_point_obs = o.min_point_observations;
+    a.max_iter = o.max_iterations;
+    a.huber = o.huber_delta;
+    a.max_err = o.max_reproj_error;
+    a.huber2 = a.huber * a.huber;
+    a.max_err2 = a.max_err * a.max_err;
+}
+
+// a host copy of the state -> the stats' iterations / cost / obs
+inline void state_to_stats(const BAState& hs, vx_ba_stats* s) {
+    s->iterations = hs.iterations;
+    for (int i = 0; i < 16; ++i) {
+        s->cost[i] = hs.cost[i];
+        s->obs[i] = hs.obs[i];
+    }
+}
+
+// A lean plan's run (ba_lean.hip): the kernels' record as the lean build fills it (n_opt and n_lm stay
+// 0: the kernels read them from a.dyn on the device) and what the record does not hold, the landmark
+// stage's capacity grid.  ba_run_dyn enqueues its a.max_iter iterations of the two-kernel LDS path
+// (k_pose_kf, k_landmark_solve; surplus workgroups exit) without a host synchronisation.
 struct DynPlan {
-    int n_kf = 0, n_split = 1, grid_blocks = 0;
-    vx_ba_options opt{};
-    const double* kf_pose0 = nullptr;
-    double* kf_pose = nullptr;
-    const double* kf_intr = nullptr;
-    double* kf_rot = nullptr;
-    const int* kf_flags = nullptr;
-    const int* kf_obs_ptr = nullptr;
-    double* kf_part = nullptr;
-    double* kf_cost = nullptr;
-    const double* lm_pos0 = nullptr;
-    double* lm_pos = nullptr;
-    const double2* pobs_uv = nullptr;
-    const int* pobs_lm = nullptr;
-    const int* lobs_ptr = nullptr;
-    const int* lobs_kf = nullptr;
-    const int* lobs_lm = nullptr;
-    const int* lm_blk = nullptr;
-    const double2* lobs_uv = nullptr;
-    void* state = nullptr;
-    const int* dyn = nullptr;
+    BAArgs a{};
+    int grid_blocks = 0;
 };
 int ba_run_dyn(vx_ctx* c, const DynPlan& d);
-size_t ba_state_bytes();
-size_t ba_state_iter_offset();  // byte offset of BAState::iterations (the run's last iteration count)
-// a host copy of BAState -> the stats' iterations / cost / obs
-void ba_state_to_stats(const void* host_state, vx_ba_stats* s);
-constexpr int kBaStrideDoubles = 32;  // (= kBaStride: doubles per pose-stage partial block)
 }  // namespace vx
