@@ -1218,6 +1218,72 @@ int vx_dmap_create_keyframes_rig(vx_ctx* ctx, vx_dmap* map, int n_cams, const vx
                                  uint64_t first_landmark_id, const vx_keyframe_options* opt,
                                  vx_keyframe_result* results);
 
+/* ---------------------------------------------------------------- relocalisation (reloc.hip)
+ * <- Tracking::TrackWithPnP (tracking.cpp:332-455) against the landmarks of up to 16 keyframes at once: what
+ *    HandleTrackingBad / HandleTrackingLost (tracking.cpp:477-499) leave as a TODO ("for now just
+ *    re-initialise", after map_->removeAll()).  ONE correspondence set is built from all candidates and ONE
+ *    PnP is solved on it, so a landmark the current frame does not see through one keyframe is found
+ *    through another; one stream-ordered sequence, one synchronisation, a launch count that does not
+ *    depend on the number of candidates:
+ *
+ *      Match(kf_c, curr) for all c -> k_reloc_pairs -> k_reloc_pool -> k_pnp_* (P = 1) -> k_reloc_final
+ *
+ *    Per candidate c (the caller's order): Match(kf_c, curr) with `ratio`, the distance filter (:342-355)
+ *    and the pair list by the rules of :373-400 — exactly what vx_track_pnp_async builds.  A candidate is
+ *    OPEN when n_good_matches >= min_matches (:357); closed candidates contribute nothing.
+ *    Pool: the open candidates' pairs concatenated, candidate-major, in pair order inside a candidate.  Of
+ *    all pairs that name the same current feature (train_idx) exactly one is kept: the smallest match
+ *    distance wins, ties go to the lower candidate index, further ties to the lower pair index.  The
+ *    survivors keep the concatenation order; pool_cand / pool_match (index into that candidate's match
+ *    list) / pool_train give each survivor's origin.  Two different current features that claim the same
+ *    landmark are left to RANSAC.
+ *    Solve: n_pool < min_inliers is FEW_PAIRS and PnP does not run.  Otherwise solvePnPRansac as
+ *    TrackWithPnP calls it: max_iterations < 0 = min(100, 2 * n_pool), resolved on the device; the seed,
+ *    the LM refit and the gates (:425, :441) of vx_track_pnp_*.
+ *    Consequence: with one candidate and no repeated train_idx the pooled arrays are TrackWithPnP's own,
+ *    and the PnP record and the mask are vx_track_pnp_fetch's byte for byte. */
+#define VX_MAX_RELOC_CANDIDATES 16          /* = VX_MAX_MATCH_PAIRS */
+typedef struct {
+    uint64_t kf_id;                      /* a live keyframe of `map` ... */
+    const vx_frame* frame;               /* ... whose features are this frame's rows */
+} vx_reloc_candidate;
+typedef struct {
+    int32_t n_matches, n_good_matches, n_pairs, n_bad_index;   /* as vx_track_pnp_fetch reports them for Match(kf_c, curr) */
+    int32_t open;            /* n_good_matches >= min_matches (:357) */
+    int32_t n_kept;          /* pairs of this candidate that survive the pool */
+    int32_t n_inliers;       /* pooled inliers that came from this candidate */
+    float   min_distance;
+    double  parallax;        /* ComputeParallax(kf_c, curr, good matches), as vx_track_result.parallax */
+} vx_reloc_candidate_result;
+typedef struct {
+    int32_t status;          /* VX_TRACK_OK | FEW_MATCHES (no candidate open) | FEW_PAIRS (n_pool < min_inliers) | PNP_FAILED | BAD_ROTATION */
+    int32_t n_cand, n_pool, best_cand;      /* best_cand: most n_inliers, ties -> lower index; -1 unless OK */
+    double  parallax;        /* cand[best_cand].parallax; 0 unless OK */
+    vx_pnp_result pnp;       /* as vx_pnp_ransac on the pooled arrays; zeros when it did not run */
+    vx_reloc_candidate_result cand[VX_MAX_RELOC_CANDIDATES];   /* entries n_cand and up are zero */
+} vx_reloc_result;
+/* n_cand in [1, VX_MAX_RELOC_CANDIDATES]; the candidates distinct live keyframes of `map`; every frame on
+ * ctx's device: anything else is VX_ERR_INVALID and leaves the previous call's result in place.  k_reloc_pool
+ * keeps one 64-bit key per current feature in LDS: a current frame whose capacity exceeds
+ * vx_relocalize_table_limit (at least 4096 rows) is refused with VX_ERR_CAPACITY; there is no second path.
+ * Ordering towards the map's context as in vx_track_pnp_async.  The call owns all of its buffers, so any
+ * vx_track_*, vx_pnp_ransac or vx_match_* call may run on ctx between the enqueue and the fetch, and this
+ * call between theirs.  May block at its start until the PREVIOUS call's argument table has left the pinned
+ * staging it reuses. */
+int vx_relocalize_async(vx_ctx* ctx, vx_dmap* map, int n_cand, const vx_reloc_candidate* cands, const vx_frame* curr,
+                        float ratio, const double* intr4, const vx_track_options* opt);
+/* One device-to-host copy of one packed block (record | pool_cand | pool_match | pool_train | mask) and one
+ * synchronisation.  The four arrays hold n_pool entries each; any may be NULL.  VX_ERR_CAPACITY (with *out
+ * filled) if an array is given and n_pool > cap_pool; VX_ERR_STATE when nothing was enqueued. */
+int vx_relocalize_fetch(vx_ctx* ctx, vx_reloc_result* out, uint8_t* pool_cand, int32_t* pool_match, int32_t* pool_train,
+                        uint8_t* mask, int cap_pool);
+/* Candidate cand's device match list Match(kf_cand, curr), as vx_track_frame_matches: what
+ * vx_dmap_create_keyframe_frame takes.  Valid until the next vx_relocalize_async on ctx. */
+int vx_relocalize_matches(vx_ctx* ctx, int cand, const vx_match** d_matches, const int32_t** d_n, int32_t* cap);
+/* The largest current-frame capacity vx_relocalize_async accepts on ctx's device: what is left of a
+ * compute unit's 160 KiB of LDS beside k_reloc_pool's own use, in 8-byte keys. */
+int vx_relocalize_table_limit(vx_ctx* ctx, int32_t* rows);
+
 /* ---------------------------------------------------------------- recorded enqueue sequences
  * A list of the async calls above (event waits / records, vx_orb_extract_async,
  * vx_match_device_async, vx_ba_plan_run_async), recorded once with every argument and replayed by

@@ -177,7 +177,8 @@ static const char* kStageNames[vx::kStCount] = {
     "frame_capture",  "track_gate",    "track_final",
     "rig_pairs",      "rig_pack",      "rig_gate",        "rig_epairs",  "rig_epose",
     "rig_final",      "frame_capture_batch",
-    "rig_kf_feat",    "rig_kf_match",  "rig_kf_count",    "rig_kf_commit"};
+    "rig_kf_feat",    "rig_kf_match",  "rig_kf_count",    "rig_kf_commit",
+    "reloc_pairs",    "reloc_pool",    "reloc_final"};
 
 extern "C" {
 

@@ -88,6 +88,9 @@ enum Stage : int {
     kStRigKfMatch,    // its triangulation gate per match (k_rig_kf_match)
     kStRigKfCount,    // the cameras' landmark counts (k_rig_kf_count)
     kStRigKfCommit,   // the cameras' ordered compactions and the map edit (k_rig_kf_commit)
+    kStRelocPairs,    // relocalisation: k_track_pairs' stages, candidate = workgroup (k_reloc_pairs)
+    kStRelocPool,     // the candidates' pairs pooled, one per current feature (k_reloc_pool)
+    kStRelocFinal,    // the record: status, per-candidate counts, best candidate (k_reloc_final)
     kStCount
 };
 
@@ -350,6 +353,25 @@ struct vx_ctx {
     int tr_n = 0;                // cameras of the enqueued call
     int64_t tr_bytes = 0;        // of the packed result
     bool tr_valid = false, tr_fetched = false, tr_fetched_kp = false;
+
+    // ---- relocalisation (reloc.hip): buffers of its own throughout, so any track, match or RANSAC call may be
+    // in flight on the same context
+    vx::StagedUpload rl_tab;     // the per-candidate argument table, staged for one upload
+    vx::DevBuf rl_match;         // match scratch, every candidate's list and count
+    vx::DevBuf rl_work;          // kept-match lists, pair segments, the candidates' packed PnP blocks and problem
+                                 // records, the pooled arrays, the pool's problem record, the PnP result
+    vx::DevBuf rl_hyp;           // hypothesis scratch
+    vx::DevBuf rl_out;           // the packed result: record | pool_cand | pool_match | pool_train | mask
+    vx::PinnedBuf rl_host;
+    struct RelocCand {
+        const vx_match* list = nullptr;
+        const int32_t* count = nullptr;
+        int cap = 0;
+    } rl_cand[VX_MAX_RELOC_CANDIDATES];
+    int rl_n = 0;                // candidates of the enqueued call
+    int rl_cap = 0;              // pool capacity of the enqueued call (sizes the packed result)
+    int rl_limit = 0;            // k_reloc_pool's LDS table limit on this device (0: not asked yet)
+    bool rl_valid = false;
 
     // ---- device-side LocalBA plan build scratch (ba_window.hip)
     struct PlanScratch {

@@ -12,7 +12,8 @@
 //   CreateKeyFrame       KeyFrameLandmarks::CreateKeyFrame                 (:577-584)
 //   CullLandmarks / CullKeyFrames   MapCulling                             (:78-81)
 //   local_ba_->Optimize  LocalBA over the DeviceMap                        (:82-84)
-//   HandleTrackingBad / Lost   Map::removeAll + DeviceMap::removeAll       (:477-499)
+//   HandleTrackingBad / Lost   Map::removeAll + DeviceMap::removeAll       (:477-499); with UseRelocalisation,
+//                              FrameTracker::Relocalize against the map's latest keyframes first
 //
 // It owns the DeviceMap that mirrors `map`; the map handed to the constructor must be empty (or be
 // mirrored by hand through ResidentMap()).  VisualizeFeatures is not ported.
@@ -91,6 +92,21 @@ public:
     void UseResidentFrames(bool on);
     bool ResidentFrames() const { return resident_; }
 
+    // Relocalisation (opt-in, before the first frame; requires UseResidentFrames(true)).  The
+    // reference's HandleTrackingBad and HandleTrackingLost (tracking.cpp:477-499) carry a TODO, "for now just
+    // re-initialise", and throw the whole map away.  With max_candidates > 0 both first relocalise
+    // current_frame_ (FrameTracker::Relocalize: one enqueue, one fetch) against RelocCandidates(*map_,
+    // max_candidates).  On success last_keyframe_ becomes the best keyframe, last_inliers_ / last_parallax_ are the
+    // record's, and the frame goes on through :76-88 exactly as after a successful Track(); on failure the
+    // reference's reset runs.  0 (default): off.  Throws std::logic_error after the first frame or without resident
+    // frames, std::invalid_argument outside [0, VX_MAX_RELOC_CANDIDATES].
+    void UseRelocalisation(int max_candidates);
+    int Relocalisation() const { return reloc_candidates_; }
+    // the candidates: the max_candidates keyframes of `map` with the highest ids whose frames hold a resident
+    // handle, most recent first
+    static std::vector<Frame::Ptr> RelocCandidates(const Map& map, int max_candidates);
+    bool LastFrameRelocalised() const { return relocalised_; }               // the last ProcessFrame relocalised its frame
+
     State GetState() const { return state_; }
 
     // read-only views of the private members (tracking.h:105-122) and of the last calls
@@ -110,8 +126,9 @@ private:
     bool Track();
     void UpdateTrackingState();
     void HandleTrackingFailure();
-    void HandleTrackingBad();
-    void HandleTrackingLost();
+    bool HandleTrackingBad();   // true: current_frame_ was relocalised and goes on as a tracked frame
+    bool HandleTrackingLost();
+    bool Relocalise();
     void Reset();
     bool NeedNewKeyFrame() const;
     void CreateKeyFrame();
@@ -139,6 +156,8 @@ private:
     vx_init_gate_result last_gate_{};
     std::vector<float> xy_;
     bool resident_ = false;
+    int reloc_candidates_ = 0;
+    bool relocalised_ = false;
 };
 
 }  // namespace visionx

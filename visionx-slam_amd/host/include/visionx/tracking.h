@@ -147,8 +147,20 @@ public:
     int RigLastInliers(size_t cam) const { const RigState& r = rig_.at(cam); return r.used_fallback ? r.ess_inliers : r.pnp_inliers; }
     double RigLastParallax(size_t cam) const { const RigState& r = rig_.at(cam); return r.used_fallback ? r.ess_parallax : r.pnp_parallax; }
     const vx_track_frame_result& RigResult(size_t cam) const { return rig_.at(cam).result; }
-    // The device match list the last resident call (TrackResident, EstimateInitialPoseResident or TrackRig:
-    // each keeps its own) holds for Match(query, train), by frame ids
+    // Relocalisation (csrc/reloc.hip; what tracking.cpp:477-499 leaves as a TODO): TrackWithPnP of `current`
+    // against the landmarks of all `keyframes` at once, as ONE vx_relocalize_async and one fetch.  keyframes: 1 ..
+    // VX_MAX_RELOC_CANDIDATES distinct keyframes of the resident map, each with a resident handle, in the order
+    // they are to be tried (std::invalid_argument otherwise; an empty list, a null current frame or one without a
+    // camera returns false without a device call).  On success it sets the pose, UsedFallback() = false,
+    // LastInliers() (the pooled PnP's inliers) and LastParallax() (the best keyframe's, as TrackWithPnP computes
+    // it) and RelocBestKeyFrame(): the candidate most pooled inliers came from, whose device match list
+    // MatchList then finds, so that KeyFrameLandmarks::CreateKeyFrame(RelocBestKeyFrame(), current) reuses it.
+    // Either way it fills current->Features() as TrackResident does (one more fetch, of the frame's rows).
+    bool Relocalize(const std::vector<Frame::Ptr>& keyframes, const Frame::Ptr& current);
+    const Frame::Ptr& RelocBestKeyFrame() const { return reloc_best_; }        // null after a failed Relocalize
+    const vx_reloc_result& LastRelocResult() const { return reloc_; }
+    // The device match list the last resident call (TrackResident, EstimateInitialPoseResident, TrackRig or
+    // Relocalize: each keeps its own) holds for Match(query, train), by frame ids
     // (tracking.cpp:340 and :863, and :208 and :863, match the same two frames): false when it holds none.
     bool MatchList(uint64_t query_id, uint64_t train_id, const vx_match** d_matches, const int32_t** d_n, int32_t* cap) const;
     // Resident calls use ONE ratio for both matches (the matcher's nn_ratio, set by Tracking::UseResidentFrames);
@@ -186,6 +198,11 @@ private:
         bool list_valid[2] = {false, false};
     };
     std::vector<RigState> rig_;
+    // the last Relocalize: its record, its best keyframe and the (query, train) ids of that candidate's device list
+    vx_reloc_result reloc_{};
+    Frame::Ptr reloc_best_;
+    uint64_t reloc_ids_[2] = {0, 0};
+    int reloc_slot_ = -1;  // the best candidate's index in the last vx_relocalize_async (-1: no list)
 };
 
 }  // namespace visionx

@@ -71,10 +71,27 @@ void Tracking::UseResidentFrames(bool on) {
     resident_ = on;
 }
 
+void Tracking::UseRelocalisation(int max_candidates) {
+    if (current_frame_) throw std::logic_error("Tracking::UseRelocalisation: only before the first frame");
+    if (max_candidates < 0 || max_candidates > VX_MAX_RELOC_CANDIDATES)
+        throw std::invalid_argument("Tracking::UseRelocalisation: max_candidates outside [0, VX_MAX_RELOC_CANDIDATES]");
+    if (max_candidates > 0 && !resident_) throw std::logic_error("Tracking::UseRelocalisation: requires UseResidentFrames(true)");
+    reloc_candidates_ = max_candidates;
+}
+
+std::vector<Frame::Ptr> Tracking::RelocCandidates(const Map& map, int max_candidates) {
+    std::vector<Frame::Ptr> out;
+    const auto& kfs = map.KeyFrames();  // ascending ids
+    for (auto it = kfs.rbegin(); it != kfs.rend() && (int)out.size() < max_candidates; ++it)
+        if (it->second && it->second->Resident()) out.push_back(it->second);
+    return out;
+}
+
 // ================= the entry point (tracking.cpp:39-89) =================
 
 void Tracking::ProcessFrame(Frame::Ptr frame) {
     current_frame_ = frame;
+    relocalised_ = false;
 
     if (resident_) {
         if (auto* orb = dynamic_cast<ORBExtractor*>(extractor_.get())) {
@@ -105,11 +122,9 @@ void Tracking::ProcessFrame(Frame::Ptr frame) {
             return;  // last_frame_ stays
         }
     } else if (state_ == State::TRACKING_BAD) {
-        HandleTrackingBad();
-        return;
+        if (!HandleTrackingBad()) return;
     } else if (state_ == State::LOST) {
-        HandleTrackingLost();
-        return;
+        if (!HandleTrackingLost()) return;
     }
 
     if (!just_initialized && NeedNewKeyFrame()) {
@@ -214,9 +229,30 @@ void Tracking::Reset() {
     last_parallax_ = 0.0;
 }
 
-void Tracking::HandleTrackingBad() { Reset(); }
+// The reference's TODO (:477-499): before the map is thrown away, one PnP of current_frame_ over the landmarks
+// of the map's latest keyframes.  On success the frame is a tracked frame (:76-88 follow in ProcessFrame).
+bool Tracking::Relocalise() {
+    if (reloc_candidates_ <= 0) return false;
+    const std::vector<Frame::Ptr> cands = RelocCandidates(*map_, reloc_candidates_);
+    if (!tracker_.Relocalize(cands, current_frame_)) return false;
+    last_keyframe_ = tracker_.RelocBestKeyFrame();
+    last_parallax_ = tracker_.LastParallax();
+    last_inliers_ = tracker_.LastInliers();
+    relocalised_ = true;
+    return true;
+}
 
-void Tracking::HandleTrackingLost() { Reset(); }
+bool Tracking::HandleTrackingBad() {
+    if (Relocalise()) return true;
+    Reset();
+    return false;
+}
+
+bool Tracking::HandleTrackingLost() {
+    if (Relocalise()) return true;
+    Reset();
+    return false;
+}
 
 // ================= keyframes (tracking.cpp:562-584) =================
 

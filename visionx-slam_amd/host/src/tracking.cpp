@@ -158,6 +158,8 @@ bool FrameTracker::MatchList(uint64_t query_id, uint64_t train_id, const vx_matc
         for (int which = 0; which < 2; ++which)
             if (r.slot >= 0 && r.list_valid[which] && r.list_ids[which][0] == query_id && r.list_ids[which][1] == train_id)
                 return vx_track_rig_matches(pnp_.map_->context(), r.slot, which, d_matches, d_n, cap) == VX_OK;
+    if (reloc_slot_ >= 0 && reloc_ids_[0] == query_id && reloc_ids_[1] == train_id)
+        return vx_relocalize_matches(pnp_.map_->context(), reloc_slot_, d_matches, d_n, cap) == VX_OK;
     return false;
 }
 
@@ -336,6 +338,46 @@ std::vector<bool> FrameTracker::TrackRig(const std::vector<RigCamera>& cams) {
         ok[i] = true;
     }
     return ok;
+}
+
+bool FrameTracker::Relocalize(const std::vector<Frame::Ptr>& keyframes, const Frame::Ptr& current) {
+    reloc_best_.reset();
+    reloc_slot_ = -1;
+    reloc_ = vx_reloc_result{};
+    if (!current || keyframes.empty() || !current->GetCamera()) return false;
+    if (keyframes.size() > (size_t)VX_MAX_RELOC_CANDIDATES)
+        throw std::invalid_argument("FrameTracker::Relocalize: more than VX_MAX_RELOC_CANDIDATES keyframes");
+    if (!current->Resident()) throw std::invalid_argument("FrameTracker: a frame without a resident handle");
+    std::vector<vx_reloc_candidate> table;
+    for (const Frame::Ptr& k : keyframes) {
+        if (!k || !k->Resident()) throw std::invalid_argument("FrameTracker: a frame without a resident handle");
+        table.push_back({k->Id(), k->Resident()->handle()});
+    }
+    const auto cam = current->GetCamera();
+    const double intr[4] = {cam->fx(), cam->fy(), cam->cx(), cam->cy()};
+    DeviceMap::Ptr& map = pnp_.map_;
+    map->Flush();
+    vx_track_options po;
+    vx_track_default_options(&po);
+    po.min_matches = pnp_.options_.min_matches;
+    po.min_inliers = pnp_.options_.min_inliers;
+    po.pnp.reproj_error = pnp_.options_.max_reproj_error;
+    vx_ctx* c = map->context();
+    int rc = vx_relocalize_async(c, map->handle(), (int)table.size(), table.data(), current->Resident()->handle(),
+                                 pnp_.options_.nn_ratio, intr, &po);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_relocalize_async: ") + vx_last_error(c));
+    rc = vx_relocalize_fetch(c, &reloc_, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc != VX_OK) throw std::runtime_error(std::string("vx_relocalize_fetch: ") + vx_last_error(c));
+    Materialize(c, *current, false);  // Features() as TrackResident leaves them
+    if (reloc_.status != VX_TRACK_OK) return false;
+    used_fallback_ = false;
+    SetPose7(current, reloc_.pnp.pose);  // (:443-450)
+    pnp_.last_parallax_ = reloc_.parallax;
+    pnp_.last_inliers_ = reloc_.pnp.n_inliers;
+    reloc_slot_ = reloc_.best_cand;
+    reloc_best_ = keyframes[(size_t)reloc_.best_cand];
+    reloc_ids_[0] = reloc_best_->Id(), reloc_ids_[1] = current->Id();
+    return true;
 }
 
 bool FrameTracker::EstimateInitialPoseResident(const Frame::Ptr& init, const Frame::Ptr& current) {

@@ -111,6 +111,7 @@ EXPORTS = [
     "vx_frame_capture_batch_async", "vx_track_rig_async", "vx_track_rig_fetch", "vx_track_rig_pairs",
     "vx_track_rig_keypoints", "vx_track_rig_matches", "vx_track_rig_layout", "vx_track_rig_block",
     "vx_dmap_create_keyframes_rig",
+    "vx_relocalize_async", "vx_relocalize_fetch", "vx_relocalize_matches", "vx_relocalize_table_limit",
 ]
 
 DEPTH_TYPES = {np.dtype(np.uint16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}
@@ -245,6 +246,12 @@ def lib():
         L.vx_track_rig_layout.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.vx_track_rig_block.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int]
+        L.vx_relocalize_async.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                          C.c_void_p]
+        L.vx_relocalize_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.vx_relocalize_matches.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_int32)]
+        L.vx_relocalize_table_limit.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.vx_cull_default_options.restype = None
         L.vx_cull_default_options.argtypes = [C.c_void_p]
         L.vx_dmap_cull_landmarks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -391,6 +398,18 @@ def rig_camera(curr, intr, last_kf_id=0, last_kf=None, last=None, pose_last=None
     T_lw of `last` (None: identity)"""
     return {"last_kf_id": int(last_kf_id), "last_kf": last_kf, "last": last, "curr": curr, "intr": intr,
             "pose_last": pose_last}
+
+
+MAX_RELOC_CANDIDATES = 16  # VX_MAX_RELOC_CANDIDATES
+
+# vx_reloc_candidate / vx_reloc_candidate_result / vx_reloc_result (include/vx_slam.h; sizes pinned in csrc/reloc.hip)
+RELOC_CANDIDATE_DTYPE = np.dtype([("kf_id", "<u8"), ("frame", "<u8")])
+RELOC_CANDIDATE_RESULT_DTYPE = np.dtype([("n_matches", "<i4"), ("n_good_matches", "<i4"), ("n_pairs", "<i4"),
+                                         ("n_bad_index", "<i4"), ("open", "<i4"), ("n_kept", "<i4"), ("n_inliers", "<i4"),
+                                         ("min_distance", "<f4"), ("parallax", "<f8")])
+RELOC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_cand", "<i4"), ("n_pool", "<i4"), ("best_cand", "<i4"),
+                               ("parallax", "<f8"), ("pnp", PNP_RESULT_DTYPE),
+                               ("cand", RELOC_CANDIDATE_RESULT_DTYPE, MAX_RELOC_CANDIDATES)])
 
 
 def track_rig_layout(cap_pairs0, cap_pairs1, cap_kp):
@@ -930,6 +949,43 @@ class Context:
         d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
         self._check(lib().vx_track_rig_matches(self._h, int(cam), int(which), C.byref(d), C.byref(n), C.byref(cap)))
         return d.value, n.value, cap.value
+
+    def relocalize_async(self, dmap, cands, curr, intr, opts=None, ratio: float = 0.8):
+        """TrackWithPnP against the landmarks of up to MAX_RELOC_CANDIDATES keyframes as ONE pooled PnP
+        (vx_relocalize_async): cands is a list of (kf_id, Frame) pairs in the caller's order, curr the current
+        Frame, opts a track_options() record.  Nothing synchronises; relocalize_fetch() completes it."""
+        opts = np.ascontiguousarray(track_options() if opts is None else opts, TRACK_OPTIONS_DTYPE)
+        intr = np.ascontiguousarray(intr, np.float64)
+        assert intr.size == 4
+        tab = np.zeros(max(len(cands), 1), RELOC_CANDIDATE_DTYPE)
+        for r, (kf_id, frame) in zip(tab, cands):
+            r["kf_id"], r["frame"] = int(kf_id), 0 if frame is None else int(frame.handle.value or 0)
+        self._check(lib().vx_relocalize_async(self._h, None if dmap is None else dmap.handle, len(cands), _p(tab),
+                                              None if curr is None else curr.handle, ratio, _p(intr), _p(opts)))
+
+    def relocalize_fetch(self, cap: int = 8192):
+        """The last relocalize_async in one copy and one synchronisation: a dict of `result` (RELOC_RESULT_DTYPE),
+        `pool_cand` (uint8), `pool_match`, `pool_train` (int32) and `mask` (uint8), n_pool entries each."""
+        out = np.zeros(1, RELOC_RESULT_DTYPE)
+        pc, mask = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.uint8)
+        pm, pt = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        self._check(lib().vx_relocalize_fetch(self._h, _p(out), _p(pc), _p(pm), _p(pt), _p(mask), cap))
+        n = int(out[0]["n_pool"])
+        return {"result": out[0], "pool_cand": pc[:n].copy(), "pool_match": pm[:n].copy(), "pool_train": pt[:n].copy(),
+                "mask": mask[:n].copy()}
+
+    def relocalize_matches(self, cand: int):
+        """(device pointer of MATCH_DTYPE rows, device pointer of the int32 count, capacity) of candidate cand's
+        Match(kf_cand, curr) of the last relocalize_async, as track_frame_matches"""
+        d, n, cap = C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._check(lib().vx_relocalize_matches(self._h, int(cand), C.byref(d), C.byref(n), C.byref(cap)))
+        return d.value, n.value, cap.value
+
+    def relocalize_table_limit(self) -> int:
+        """the largest current-frame capacity relocalize_async accepts (k_reloc_pool's LDS table)"""
+        n = C.c_int32(0)
+        self._check(lib().vx_relocalize_table_limit(self._h, C.byref(n)))
+        return int(n.value)
 
     def frame_capture_batch(self, bank: int, frames):
         """frames 0 .. len(frames) - 1 of a batch bank (orb_extract_batch*) into the Frame handles in ONE
