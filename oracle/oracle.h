@@ -170,6 +170,10 @@ int orc_sba_system(const orc_map_view* map, uint64_t ref_kf_id, int has_ref,
 int orc_sba_system_shard(const orc_map_view* map, uint64_t ref_kf_id, int has_ref, const orc_sba_options* opt,
                          double lambda, int shard_rank, int shard_count, double* S, double* rhs, double* HTd,
                          double* cost_count, int n);
+/* Test hook, the counterpart of vx_sba_plan_step: the pose step dx (n = 6 * window keyframes, window
+ * order, fixed keyframes 0) of the last iteration that solved in this thread's last
+ * orc_sba_optimize_map call (all 0 when none did).  -1 when n does not match. */
+int orc_sba_last_step(double* dx, int n);
 
 /* ---- keyframe-insertion landmark creation (landmark_oracle.cpp), same contract as vx_slam.h */
 int orc_depth_landmarks(const double* feat_uv, const uint8_t* feat_has_lm, int n_feat, const void* depth,

@@ -299,6 +299,13 @@ def sba_optimize(m, opts=None, ref_kf_id=None):
     return st
 
 
+def sba_last_step(n_window_kf):
+    """orc_sba_last_step: the pose step of the last solving iteration of this thread's last sba_optimize."""
+    dx = np.zeros(6 * int(n_window_kf))
+    assert lib().orc_sba_last_step(_p(dx), dx.size) == 0
+    return dx
+
+
 def sba_system(m, opts=None, lam=None, ref_kf_id=None):
     """Reduced pose system (S, rhs) at the map's current state (None on an early return)."""
     if opts is None:

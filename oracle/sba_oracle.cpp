@@ -325,6 +325,10 @@ bool cholesky_solve(std::vector<double> A, int n, const std::vector<double>& b, 
     return true;
 }
 
+// the pose step of the last iteration of the last orc_sba_optimize_map call that solved (test hook,
+// as vx_sba_plan_step: window order, fixed keyframes 0)
+thread_local std::vector<double> g_last_dx;
+
 State initial_state(const orc_map_view* m, const Problem& P) {
     State X;
     for (int r = 0; r < P.nk; ++r) {
@@ -379,6 +383,7 @@ extern "C" int orc_sba_optimize_map(orc_map_view* m, uint64_t ref, int has_ref, 
     if (P.status != 0) return 0;
     st->status = 0;
     const int n_opt = (int)P.opt.size();
+    g_last_dx.assign((size_t)6 * P.nk, 0.0);
 
     State best = initial_state(m, P), trial = best;
     bool eval_trial = false;
@@ -429,8 +434,16 @@ extern "C" int orc_sba_optimize_map(orc_map_view* m, uint64_t ref, int has_ref, 
         }
         // back-substitution and the trial state
         trial = best;
-        for (int r = 0; r < P.nk; ++r)
-            if (!P.fixed[r]) trial.T[r] = left_update(&x[6 * r], best.T[r]);
+        g_last_dx = x;
+        for (int r = 0; r < P.nk; ++r) {
+            if (!P.fixed[r]) {
+                // a zero step is the identity: the pose keeps its bits (no quaternion renormalisation)
+                bool any = false;
+                for (int a = 0; a < 6; ++a) any = any || x[6 * r + a] != 0.0;
+                if (any) trial.T[r] = left_update(&x[6 * r], best.T[r]);
+            } else
+                for (int a = 0; a < 6; ++a) g_last_dx[6 * r + a] = 0.0;
+        }
         for (int s = 0; s < n_opt; ++s) {
             double q[3] = {sys.gp[3 * s], sys.gp[3 * s + 1], sys.gp[3 * s + 2]};
             for (int i = P.lm_ptr[s]; i < P.lm_ptr[s + 1]; ++i) {
@@ -458,5 +471,11 @@ extern "C" int orc_sba_optimize_map(orc_map_view* m, uint64_t ref, int has_ref, 
         double* q = m->lm_pos + 3 * P.opt[s];
         q[0] = best.p[s].x; q[1] = best.p[s].y; q[2] = best.p[s].z;
     }
+    return 0;
+}
+
+extern "C" int orc_sba_last_step(double* dx, int n) {
+    if (!dx || n != (int)g_last_dx.size()) return -1;
+    for (int i = 0; i < n; ++i) dx[i] = g_last_dx[i];
     return 0;
 }

@@ -1562,13 +1562,16 @@ __global__ __launch_bounds__(kUpdThreads) void k_sba_update(SBAArgs a, int it) {
         for (int j = 0; j < 8; ++j) T[j] = Tb[8 * t + j];
         if (!(a.kf_flags[t] & 2)) {
             double d[6];
-            bool fin = true;
+            bool fin = true, any = false;
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 d[j] = a.dx[6 * t + j];
                 fin = fin && isfinite(d[j]);
+                any = any || d[j] != 0.0;
             }
-            if (fin) se3_left_update(d, T);
+            // a zero step (a keyframe whose every observation is gated: rhs 0) is the identity: the pose
+            // keeps its bits — se3_left_update would renormalise the quaternion, an ulp per accepted step
+            if (fin && any) se3_left_update(d, T);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) Tt[8 * t + j] = T[j];
